@@ -16,6 +16,11 @@ kernels for conv/BN/ReLU/optimizer/loss and the framework's own RCCL gradient bu
 ``--impl torch`` runs stock PyTorch-ROCm (MIOpen convs, torch DDP) on the same model
 and data, which is the measured comparison baseline (BASELINE.md has no published
 number).
+
+A plain run sets up, warms up, times ``--steps`` steps and prints one JSON result line;
+``--dump-outputs DIR`` also writes what the last timed step computed as ``DIR/<name>.npy``
+(model weights and data are seeded, so two builds can be compared output for output).
+``--full`` is where measurements beyond the headline figure go; there are none today.
 """
 from __future__ import annotations
 
@@ -55,7 +60,56 @@ def parse():
     p.add_argument('--comm', default='auto', choices=['auto', 'rccl1'],
                    help='rccl1: give a one-GPU run a world-1 RCCL communicator, so the production gradient '
                         'bucketer issues its RCCL all-reduces on the side stream (overlap evidence)')
+    p.add_argument('--dump-outputs', default=None, metavar='DIR',
+                   help='after the timed steps, write what the last step computed (loss, updated parameters, '
+                        'BatchNorm running statistics) as DIR/<name>.npy')
+    p.add_argument('--full', action='store_true',
+                   help='also run the measurements beyond the headline figure (there are none today: a plain '
+                        'run already does only setup, warmup, the timed steps and the result line)')
     return p.parse_args()
+
+
+# --dump-outputs: an array longer than this is written as a fixed sample of its elements
+# (seeded, sorted positions).  A dump holds the loss and at most three such arrays, which
+# keeps it under 64 MB
+DUMP_MAX_ELEMS = 4 * 1024 * 1024
+
+
+def _dump_outputs(step, loss, path):
+    """Write what the step's caller holds after the last timed step: the loss, the updated
+    fp32 parameters and the BatchNorm running statistics, each as ``<name>.npy`` (float32;
+    the loss float64).  The native steps keep their parameters in two flat arenas
+    (mlcomp_amd.ops.arena: ``params_decay``, ``params_nodecay``); the torch steps in
+    ``model.parameters()``, concatenated in registration order (``params``).
+
+    Weights and data are seeded, so two runs start from the same state; what differs between
+    them afterwards is the order of the kernels' floating-point atomic adds, carried through
+    the warmup and timed steps of training (``MLC_DETERMINISTIC=1`` removes it)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    arrays = {'loss': np.asarray([float('nan') if loss is None else loss], dtype=np.float64)}
+    net = getattr(step, 'net', None)
+    arena = getattr(net, 'arena', None) or getattr(step, 'arena', None)
+    model = getattr(step, 'model', None)
+    if arena is not None and hasattr(arena, 'arenas'):
+        for a in arena.arenas():
+            arrays[f'params_{a.name}'] = a.master
+    elif isinstance(model, torch.nn.Module):
+        arrays['params'] = torch.cat([p.detach().float().reshape(-1) for p in model.parameters()])
+        bufs = [b.detach().float().reshape(-1) for b in model.buffers() if b.is_floating_point()]
+        if bufs:
+            arrays['bn_buffers'] = torch.cat(bufs)
+    if getattr(step, 'bn_buffers', None) is not None:
+        arrays['bn_buffers'] = step.bn_buffers
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().float().reshape(-1)
+            if a.numel() > DUMP_MAX_ELEMS:
+                idx = np.sort(np.random.default_rng(0).choice(a.numel(), DUMP_MAX_ELEMS, replace=False))
+                a = a[torch.from_numpy(idx).to(a.device)]
+            a = a.cpu().numpy().astype(np.float32, copy=False)
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def _world1_rccl(device):
@@ -141,6 +195,7 @@ def main():
     if comm is not None and getattr(step, 'bucketer', None) is not None:
         step.bucketer.op = 'avg'     # world 1: scale 1.0, but RCCL launches its kernel per bucket
     feed = None
+    engine = step
     if args.data == 'records':
         if is_bert or is_unet:
             print('--data records feeds the image classifiers only', file=sys.stderr)
@@ -178,6 +233,8 @@ def main():
     images = args.batch * world * args.steps
     value = images / elapsed
     loss = step.last_loss()
+    if rank == 0 and args.dump_outputs:
+        _dump_outputs(engine, loss, args.dump_outputs)
     if rank == 0 and feed is not None:
         out = {
             'metric': 'images/sec (whole node) ResNet-50 DAG train task, record-file input pipeline',

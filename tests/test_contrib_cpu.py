@@ -114,7 +114,7 @@ def test_image_datasets(tmp_path):
 
     class RefStyle(ImageDataset):
         # a subclass written against the reference's hooks
-        # (/root/reference/mlcomp/contrib/dataset/classify.py:82-114)
+        # (`mlcomp/contrib/dataset/classify.py:82-114`)
         def _get_item_before_transform(self, row, item):
             item['image'] = item['image'] * 0 + 7
 

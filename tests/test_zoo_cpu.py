@@ -10,7 +10,8 @@ import torch
 from mlcomp_amd.models import MODELS, build_model, _populate
 from mlcomp_amd.contrib.presets import load_preset, preset_names
 
-REF_PRESETS = '/root/reference/mlcomp/contrib/catalyst/configs/classify'
+# the reference's preset list (its configs/classify/*.yml, names only), stored with the tests
+REF_PRESETS = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'classify_preset_names.txt')
 
 # published parameter counts (torch, running statistics excluded), in millions
 PARAMS = {'xception': 22.855952, 'inceptionv3': 23.834568, 'inceptionv4': 42.679816, 'bninception': 11.295240,
@@ -27,9 +28,10 @@ def test_every_preset_names_a_registered_model():
     import mlcomp_amd.models.zoo as zoo
     zoo._register_encoder_classifiers()
     names = preset_names()
-    if os.path.isdir(REF_PRESETS):   # the reference's preset list, when it is mounted
-        ref = {f[:-4] for f in os.listdir(REF_PRESETS) if f.endswith('.yml')}
-        assert ref <= set(names), sorted(ref - set(names))
+    with open(REF_PRESETS) as f:
+        ref = {line.strip() for line in f if line.strip()}
+    assert len(ref) == 33, len(ref)
+    assert ref <= set(names), sorted(ref - set(names))
     for n in names:
         assert load_preset(n)['model_params']['variant'] in MODELS, n
 
