@@ -14,6 +14,16 @@
 // kernel's element index ((b*H + h)*S + q)*S + key (dropout.h), so every attention path
 // drops the same elements.
 //
+// Masks (the *_masked entry points; a compile-time mode of the three streaming kernels, mode 0
+// being the unmasked code): causal (query q sees keys <= q: a 128-query block streams only
+// the key tiles t < 2*blk + 2, a 128-key block only the query tiles t >= 2*blk, and only the
+// two tiles that cross the diagonal compare indices) and an additive fp32 bias
+// [b*stride_b + h*stride_h + q*S + key] read straight from global memory (forward / dQ: a
+// lane's registers are consecutive keys of one row, 16-byte loads when rows are aligned;
+// dK/dV: a register is one query row, the lanes read consecutive keys).  Masked entries get
+// -inf before the running max (forward) or in the exponent (backward), so their
+// probabilities are exactly 0 whatever the saved log-sum-exp.
+//
 // Work split (one 256-thread block = 4 waves x 32 rows, blocks XCD-remapped so the blocks
 // sharing one (b, h) K/V slice sit on one XCD's L2):
 // * forward: a wave owns 32 queries; scores are computed transposed, S^T = K Q^T
@@ -132,6 +142,32 @@ struct Tile {
   }
 };
 
+// Mask modes (a template parameter of the streaming kernels; 0 is the unmasked code).
+constexpr int M_CAUSAL = 1;   // top-left aligned: query q sees keys <= q
+constexpr int M_BIAS = 2;     // additive fp32 bias[b * sb + h * sh + q * S + key], finite or -inf
+struct AttnBias {
+  const float* p;
+  long sb, sh;   // batch / head strides in elements (0 broadcasts)
+  int vec;       // rows are 16-byte aligned (S % 4 == 0, aligned base and strides)
+};
+// bias of this lane's query row for the keys of its accumulator registers: bv[i][g][e] is
+// key k0 + 32i + 8g + e (k0 = 64t + 4*hh).  Keys past S (tail tile) are clamped in bounds;
+// their scores are -inf from the key bias already.
+__device__ __forceinline__ void load_bias_keys(f32x4 (&bv)[2][4], const float* row, int k0, int S, int vec) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int key = k0 + 32 * i + 8 * g;
+      if (vec) {
+        bv[i][g] = *reinterpret_cast<const f32x4*>(row + min(key, S - 4));
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) bv[i][g][e] = row[min(key + e, S - 1)];
+      }
+    }
+}
+
 struct Geo {
   int b, hd, bh, blk;
 };
@@ -145,16 +181,32 @@ __device__ __forceinline__ Geo geo(int H, int nblk) {
   return g;
 }
 
+// Causal blocks have unequal work (block blk of a query-block kernel streams 2*blk + 2 key
+// tiles, of a key-block kernel nt - 2*blk query tiles), so they are issued heaviest first
+// across the whole grid - slot s of every (b, h) before slot s + 1 - and the light blocks
+// that arrive last fill in beside the heavy ones.
+__device__ __forceinline__ Geo geo_heavy_first(int H, int nblk, bool last_is_heaviest) {
+  const int nbh = gridDim.x / nblk;
+  const int slot = blockIdx.x / nbh;
+  Geo g;
+  g.bh = blockIdx.x - slot * nbh;
+  g.blk = last_is_heaviest ? nblk - 1 - slot : slot;
+  g.b = g.bh / H;
+  g.hd = g.bh - g.b * H;
+  return g;
+}
+
 // ------------------------------------------------------------------ forward
-template <int D, bool DROP>
+template <int D, bool DROP, int MASK>
 __global__ void __launch_bounds__(NT)
 fwd_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, bf16* __restrict__ out,
            float* __restrict__ lse, int S, int H, int nqb, float sl2, uint32_t thr, float inv_keep,
-           const uint32_t* __restrict__ seedp, uint32_t salt) {
+           const uint32_t* __restrict__ seedp, uint32_t salt, AttnBias ab) {
   constexpr int NS = D / 16, NJ = D / 32, IMG = KT * D * 2, BUF = 2 * IMG + KT * 4;
+  constexpr bool CAUSAL = (MASK & M_CAUSAL) != 0, BIAS = (MASK & M_BIAS) != 0;
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];   // [buffer][K | V | key bias * log2e]
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, hh = lane >> 5, l32 = lane & 31;
-  const Geo G = geo(H, nqb);
+  const Geo G = CAUSAL ? geo_heavy_first(H, nqb, true) : geo(H, nqb);
   const int E = H * D, ld = 3 * E;
   const bf16* Qg = qkv + (size_t)G.b * S * ld + G.hd * D;
   const bf16* Kg = Qg + E;
@@ -188,12 +240,20 @@ fwd_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, bf1
   fetch(0);
   put(0);
   __syncthreads();
-  const int nt = (S + KT - 1) / KT;   // a partial last tile is masked
+  // a partial last tile is masked; a causal query block stops at the tile of its last query
+  const int nt = CAUSAL ? min((S + KT - 1) / KT, 2 * G.blk + 2) : (S + KT - 1) / KT;
+  const float* brow = BIAS ? ab.p + G.b * ab.sb + G.hd * ab.sh + (size_t)qc * S : nullptr;
+  const int wq_last = G.blk * 128 + 32 * __builtin_amdgcn_readfirstlane(w) + 31;   // this wave's last query
   for (int t = 0; t < nt; ++t) {
     const char* Ki = smem + (t & 1) * BUF;
     const char* Vi = Ki + IMG;
     const float* Kb = reinterpret_cast<const float*>(Ki + 2 * IMG);
     if (t + 1 < nt) fetch(t + 1);
+    // causal: a wave whose 32 queries all precede the tile's keys has nothing to add (its
+    // scores would all be -inf and contribute zero); it still stages and synchronises
+    if (!(CAUSAL && t * KT > wq_last)) {
+    f32x4 bv[2][4];
+    if constexpr (BIAS) load_bias_keys(bv, brow, t * KT + 4 * hh, S, ab.vec);
     f32x16 a[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -201,6 +261,7 @@ fwd_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, bf1
 #pragma unroll
       for (int s = 0; s < NS; ++s) a[i] = mfma(rowf<D>(Ki, 32 * i + l32, s, lane), qf[s], a[i]);
     }
+    const bool diag = CAUSAL && t >= 2 * G.blk;   // the tile crosses the diagonal (block-uniform)
     float tmax = -INFINITY;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -209,7 +270,10 @@ fwd_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, bf1
         const f32x4 k4 = *reinterpret_cast<const f32x4*>(Kb + 32 * i + 8 * g + 4 * hh);   // keys of regs 4g..4g+3
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float x = a[i][4 * g + e] * sl2 + k4[e];
+          float x = a[i][4 * g + e] * sl2 + k4[e];
+          if constexpr (BIAS) x += bv[i][g][e] * LOG2E;
+          if constexpr (CAUSAL)
+            if (diag && t * KT + 32 * i + 8 * g + 4 * hh + e > q) x = -INFINITY;
           a[i][4 * g + e] = x;
           tmax = fmaxf(tmax, x);
         }
@@ -249,6 +313,7 @@ fwd_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, bf1
 #pragma unroll
         for (int j = 0; j < NJ; ++j) o[j] = mfma(trf<D>(Vi, 32 * j, 32 * i + 16 * s, lane), pb, o[j]);
       }
+    }
     if (t + 1 < nt) put(t + 1);
     __syncthreads();
   }
@@ -265,16 +330,17 @@ fwd_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, bf1
 }
 
 // ------------------------------------------------------------------ backward: dQ (+ dot)
-template <int D, bool DROP>
+template <int D, bool DROP, int MASK>
 __global__ void __launch_bounds__(NT)
 dq_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, const bf16* __restrict__ out,
           const bf16* __restrict__ dout, const float* __restrict__ lse, float* __restrict__ dot,
           bf16* __restrict__ dqkv, int S, int H, int nqb, float scale, float sl2, uint32_t thr, float inv_keep,
-          const uint32_t* __restrict__ seedp, uint32_t salt) {
+          const uint32_t* __restrict__ seedp, uint32_t salt, AttnBias ab) {
   constexpr int NS = D / 16, NJ = D / 32, IMG = KT * D * 2, BUF = 2 * IMG + KT * 4;
+  constexpr bool CAUSAL = (MASK & M_CAUSAL) != 0, BIAS = (MASK & M_BIAS) != 0;
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];   // [buffer][K | V | key bias * log2e]
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, hh = lane >> 5, l32 = lane & 31;
-  const Geo G = geo(H, nqb);
+  const Geo G = CAUSAL ? geo_heavy_first(H, nqb, true) : geo(H, nqb);
   const int E = H * D, ld = 3 * E;
   const bf16* Qg = qkv + (size_t)G.b * S * ld + G.hd * D;
   const bf16* Kg = Qg + E;
@@ -319,12 +385,19 @@ dq_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, cons
   fetch(0);
   put(0);
   __syncthreads();
-  const int nt = (S + KT - 1) / KT;   // a partial last tile is masked
+  // a partial last tile is masked; a causal query block stops at the tile of its last query
+  const int nt = CAUSAL ? min((S + KT - 1) / KT, 2 * G.blk + 2) : (S + KT - 1) / KT;
+  const float* brow = BIAS ? ab.p + G.b * ab.sb + G.hd * ab.sh + (size_t)qc * S : nullptr;
+  const int wq_last = G.blk * 128 + 32 * __builtin_amdgcn_readfirstlane(w) + 31;   // this wave's last query
   for (int t = 0; t < nt; ++t) {
     const char* Ki = smem + (t & 1) * BUF;
     const char* Vi = Ki + IMG;
     const float* Kb = reinterpret_cast<const float*>(Ki + 2 * IMG);
     if (t + 1 < nt) fetch(t + 1);
+    if (!(CAUSAL && t * KT > wq_last)) {   // as in fwd_kernel: nothing but exact zeros to add
+    f32x4 bv[2][4];
+    if constexpr (BIAS) load_bias_keys(bv, brow, t * KT + 4 * hh, S, ab.vec);
+    const bool diag = CAUSAL && t >= 2 * G.blk;
     f32x16 sp[2], dp[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -344,7 +417,11 @@ dq_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, cons
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int r = 4 * g + e;
-          const float p = __builtin_amdgcn_exp2f(sp[i][r] * sl2 + k4[e] - l2);
+          float x = sp[i][r] * sl2 + k4[e];
+          if constexpr (BIAS) x += bv[i][g][e] * LOG2E;
+          if constexpr (CAUSAL)
+            if (diag && t * KT + 32 * i + 8 * g + 4 * hh + e > q) x = -INFINITY;   // p exactly 0
+          const float p = __builtin_amdgcn_exp2f(x - l2);
           float d = dp[i][r];
           if constexpr (DROP) d = keep(seed, salt, rowidx + t * KT + 32 * i + 8 * g + 4 * hh + e, thr) ? d * inv_keep : 0.f;
           sp[i][r] = scale * p * (d - dt);
@@ -358,6 +435,7 @@ dq_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, cons
 #pragma unroll
         for (int j = 0; j < NJ; ++j) dq[j] = mfma(trf<D>(Ki, 32 * j, 32 * i + 16 * s, lane), sb, dq[j]);
       }
+    }
     if (t + 1 < nt) put(t + 1);
     __syncthreads();
   }
@@ -365,17 +443,18 @@ dq_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, cons
 }
 
 // ------------------------------------------------------------------ backward: dK, dV
-template <int D, bool DROP>
+template <int D, bool DROP, int MASK>
 __global__ void __launch_bounds__(NT)
 dkv_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, const bf16* __restrict__ dout,
            const float* __restrict__ lse, const float* __restrict__ dot, bf16* __restrict__ dqkv, int S, int H,
            int nkb, float scale, float sl2, uint32_t thr, float inv_keep, const uint32_t* __restrict__ seedp,
-           uint32_t salt) {
+           uint32_t salt, AttnBias ab) {
   constexpr int NS = D / 16, NJ = D / 32, IMG = KT * D * 2, BUF = 2 * IMG + 2 * KT * 4;
+  constexpr bool CAUSAL = (MASK & M_CAUSAL) != 0, BIAS = (MASK & M_BIAS) != 0;
   // [buffer][Q image | dO image | lse*log2e [64] | dot [64]]
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, hh = lane >> 5, l32 = lane & 31;
-  const Geo G = geo(H, nkb);
+  const Geo G = CAUSAL ? geo_heavy_first(H, nkb, false) : geo(H, nkb);
   const int E = H * D, ld = 3 * E;
   const bf16* Qg = qkv + (size_t)G.b * S * ld + G.hd * D;
   const bf16* Kg = Qg + E;
@@ -415,17 +494,26 @@ dkv_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, con
     to.store(bp + IMG, tid);
     if (tid < 2 * KT) reinterpret_cast<float*>(bp + 2 * IMG)[tid] = ld_v;
   };
-  fetch(0);
-  put(0);
+  // causal: the first query tile that sees this key block (128 * blk < S, so t0 < nt); the
+  // staging buffers alternate on the tile's parity, whichever tile comes first
+  const int t0 = CAUSAL ? 2 * G.blk : 0;
+  fetch(t0);
+  put(t0);
   __syncthreads();
   const int nt = (S + KT - 1) / KT;   // a partial last tile is masked
-  for (int t = 0; t < nt; ++t) {
+  const float* bcol = BIAS ? ab.p + G.b * ab.sb + G.hd * ab.sh + kc : nullptr;
+  const int wk_first = G.blk * 128 + 32 * __builtin_amdgcn_readfirstlane(w);   // this wave's first key
+  for (int t = t0; t < nt; ++t) {
     const char* bp = smem + (t & 1) * BUF;
     const char* Qi = bp;
     const char* Oi = bp + IMG;
     const float* Ls = reinterpret_cast<const float*>(bp + 2 * IMG);
     const float* Ds = Ls + KT;
     if (t + 1 < nt) fetch(t + 1);
+    // causal: a wave whose 32 keys all follow the tile's queries has nothing but exact zeros
+    // to add; it still stages and synchronises
+    if (!(CAUSAL && t * KT + KT - 1 < wk_first)) {
+    const bool diag = CAUSAL && t < t0 + 2;   // the tile crosses the diagonal (block-uniform)
     f32x16 sc[2], dp[2];   // C[q][key]: lane = key, register r = query 32i + acc_row(r, hh)
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -447,7 +535,12 @@ dkv_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, con
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int r = 4 * g + e;
-          const float p = __builtin_amdgcn_exp2f(sc[i][r] * sl2 + kbl - L4[e]);
+          float x = sc[i][r] * sl2 + kbl;
+          // padded queries of a tail tile re-read the last row (their lse = +inf zeroes them)
+          if constexpr (BIAS) x += bcol[(size_t)min(t * KT + q0 + e, S - 1) * S] * LOG2E;
+          if constexpr (CAUSAL)
+            if (diag && t * KT + q0 + e < key) x = -INFINITY;   // p exactly 0
+          const float p = __builtin_amdgcn_exp2f(x - L4[e]);
           float d = dp[i][r], pd = p;
           if constexpr (DROP) {
             const bool kp = keep(seed, salt, ((uint32_t)G.bh * S + t * KT + q0 + e) * S + kc, thr);
@@ -470,6 +563,7 @@ dkv_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, con
           dk[j] = mfma(trf<D>(Qi, 32 * j, 32 * i + 16 * s, lane), sb, dk[j]);
         }
       }
+    }
     if (t + 1 < nt) put(t + 1);
     __syncthreads();
   }
@@ -751,18 +845,50 @@ bool flash_shape_ok(int B, int S, int H, int D) {
 
 }  // namespace
 
-// out [B*S][H*D] = softmax(scale * Q K^T + key_bias) V per head, lse [B*H*S] (natural log;
-// +inf for a fully masked row).  Any S >= 1 (a partial last 64-key tile is masked), D in {64, 128}.
-MLC_EXPORT int mlc_flash_fwd(const bf16* qkv, const float* key_bias, bf16* out, float* lse, int B, int S, int H,
-                             int D, float scale, float p, const uint32_t* seed, uint32_t salt, hipStream_t st) {
-  if (!flash_shape_ok(B, S, H, D)) return -1;
-  const uint32_t t = p > 0.f ? drop_threshold(p) : 0u;
-  const float k = p > 0.f ? 1.f / (1.f - p) : 1.f;
+namespace {
+
+void resolve_bwd128() {
   if (g_bwd128 < 0) {
     const char* e = getenv("MLC_ATTN_BWD128");
     g_bwd128 = e ? atoi(e) : 1;
   }
-  if (S == 128 && D == 64 && g_bwd128) {   // whole-key-range forward (MLC_ATTN_BWD128 covers both)
+}
+
+// the mask mode of a call and the bias operand the kernels take
+int mask_mode(int causal, const float* attn_bias) { return (causal ? M_CAUSAL : 0) | (attn_bias ? M_BIAS : 0); }
+AttnBias bias_arg(const float* attn_bias, long stride_b, long stride_h, int S) {
+  AttnBias ab;
+  ab.p = attn_bias;
+  ab.sb = stride_b;
+  ab.sh = stride_h;
+  ab.vec = attn_bias && S % 4 == 0 && (reinterpret_cast<uintptr_t>(attn_bias) & 15) == 0 && stride_b % 4 == 0 &&
+           stride_h % 4 == 0;
+  return ab;
+}
+
+// instantiate X(D, DROP, MASK) for the call's head dim, dropout and mask mode
+#define FLASH_DISPATCH(X)                                                     \
+  do {                                                                        \
+    if (D == 64) { if (t) { FLASH_MASKS(X, 64, true) } else { FLASH_MASKS(X, 64, false) } }   \
+    else { if (t) { FLASH_MASKS(X, 128, true) } else { FLASH_MASKS(X, 128, false) } }         \
+  } while (0)
+#define FLASH_MASKS(X, DD, DR)                  \
+  switch (mode) {                               \
+    case 0: X(DD, DR, 0); break;                \
+    case M_CAUSAL: X(DD, DR, M_CAUSAL); break;  \
+    case M_BIAS: X(DD, DR, M_BIAS); break;      \
+    default: X(DD, DR, M_CAUSAL | M_BIAS); break; \
+  }
+
+int flash_fwd(const bf16* qkv, const float* key_bias, bf16* out, float* lse, int B, int S, int H, int D, float scale,
+              float p, const uint32_t* seed, uint32_t salt, int causal, const float* attn_bias, long stride_b,
+              long stride_h, hipStream_t st) {
+  if (!flash_shape_ok(B, S, H, D)) return -1;
+  const uint32_t t = p > 0.f ? drop_threshold(p) : 0u;
+  const float k = p > 0.f ? 1.f / (1.f - p) : 1.f;
+  const int mode = mask_mode(causal, attn_bias);
+  resolve_bwd128();
+  if (S == 128 && D == 64 && g_bwd128 && !mode) {   // whole-key-range forward (MLC_ATTN_BWD128 covers both)
     const dim3 grid(B * H);
     if (t)
       hipLaunchKernelGGL((fwd128_kernel<64, true>), grid, dim3(NT), 0, st, qkv, key_bias, out, lse, H, scale * LOG2E,
@@ -774,27 +900,23 @@ MLC_EXPORT int mlc_flash_fwd(const bf16* qkv, const float* key_bias, bf16* out, 
   }
   const int nqb = (S + 127) / 128;
   const dim3 grid(B * H * nqb);
-#define FWD(DD, DR) hipLaunchKernelGGL((fwd_kernel<DD, DR>), grid, dim3(NT), 0, st, qkv, key_bias, out, lse, S, H, nqb, \
-                                       scale * LOG2E, t, k, seed, salt)
-  if (D == 64) { if (t) FWD(64, true); else FWD(64, false); }
-  else { if (t) FWD(128, true); else FWD(128, false); }
+  const AttnBias ab = bias_arg(attn_bias, stride_b, stride_h, S);
+#define FWD(DD, DR, MM) hipLaunchKernelGGL((fwd_kernel<DD, DR, MM>), grid, dim3(NT), 0, st, qkv, key_bias, out, lse, S, \
+                                           H, nqb, scale * LOG2E, t, k, seed, salt, ab)
+  FLASH_DISPATCH(FWD);
 #undef FWD
   return hipGetLastError();
 }
 
-// dqkv [B*S][3*H*D] fully overwritten (dQ | dK | dV); out = the forward's output; dot
-// [B*H*S] fp32 scratch.
-MLC_EXPORT int mlc_flash_bwd(const bf16* qkv, const float* key_bias, const bf16* out, const bf16* dout,
-                             const float* lse, float* dot, bf16* dqkv, int B, int S, int H, int D, float scale,
-                             float p, const uint32_t* seed, uint32_t salt, hipStream_t st) {
-  if (g_bwd128 < 0) {
-    const char* e = getenv("MLC_ATTN_BWD128");
-    g_bwd128 = e ? atoi(e) : 1;
-  }
+int flash_bwd(const bf16* qkv, const float* key_bias, const bf16* out, const bf16* dout, const float* lse, float* dot,
+              bf16* dqkv, int B, int S, int H, int D, float scale, float p, const uint32_t* seed, uint32_t salt,
+              int causal, const float* attn_bias, long stride_b, long stride_h, hipStream_t st) {
+  resolve_bwd128();
   if (!flash_shape_ok(B, S, H, D)) return -1;
   const uint32_t t = p > 0.f ? drop_threshold(p) : 0u;
   const float k = p > 0.f ? 1.f / (1.f - p) : 1.f;
-  if (S == 128 && D == 64 && g_bwd128) {   // whole-problem fused backward (MLC_ATTN_BWD128)
+  const int mode = mask_mode(causal, attn_bias);
+  if (S == 128 && D == 64 && g_bwd128 && !mode) {   // whole-problem fused backward (MLC_ATTN_BWD128)
     const dim3 grid(B * H);
     if (t)
       hipLaunchKernelGGL((bwd128_kernel<64, true>), grid, dim3(NT), 0, st, qkv, key_bias, out, dout, lse, dqkv, H,
@@ -806,17 +928,58 @@ MLC_EXPORT int mlc_flash_bwd(const bf16* qkv, const float* key_bias, const bf16*
   }
   const int nb = (S + 127) / 128;
   const dim3 grid(B * H * nb);
-#define BWD(DD, DR)                                                                                              \
-  do {                                                                                                           \
-    hipLaunchKernelGGL((dq_kernel<DD, DR>), grid, dim3(NT), 0, st, qkv, key_bias, out, dout, lse, dot, dqkv, S, H, \
-                       nb, scale, scale * LOG2E, t, k, seed, salt);                                              \
-    hipLaunchKernelGGL((dkv_kernel<DD, DR>), grid, dim3(NT), 0, st, qkv, key_bias, dout, lse, dot, dqkv, S, H, nb, \
-                       scale, scale * LOG2E, t, k, seed, salt);                                                  \
+  const AttnBias ab = bias_arg(attn_bias, stride_b, stride_h, S);
+#define BWD(DD, DR, MM)                                                                                              \
+  do {                                                                                                               \
+    hipLaunchKernelGGL((dq_kernel<DD, DR, MM>), grid, dim3(NT), 0, st, qkv, key_bias, out, dout, lse, dot, dqkv, S, H, \
+                       nb, scale, scale * LOG2E, t, k, seed, salt, ab);                                              \
+    hipLaunchKernelGGL((dkv_kernel<DD, DR, MM>), grid, dim3(NT), 0, st, qkv, key_bias, dout, lse, dot, dqkv, S, H, nb, \
+                       scale, scale * LOG2E, t, k, seed, salt, ab);                                                  \
   } while (0)
-  if (D == 64) { if (t) BWD(64, true); else BWD(64, false); }
-  else { if (t) BWD(128, true); else BWD(128, false); }
+  FLASH_DISPATCH(BWD);
 #undef BWD
   return hipGetLastError();
+}
+#undef FLASH_MASKS
+#undef FLASH_DISPATCH
+
+}  // namespace
+
+// out [B*S][H*D] = softmax(scale * Q K^T + key_bias) V per head, lse [B*H*S] (natural log;
+// +inf for a fully masked row).  Any S >= 1 (a partial last 64-key tile is masked), D in {64, 128}.
+MLC_EXPORT int mlc_flash_fwd(const bf16* qkv, const float* key_bias, bf16* out, float* lse, int B, int S, int H,
+                             int D, float scale, float p, const uint32_t* seed, uint32_t salt, hipStream_t st) {
+  return flash_fwd(qkv, key_bias, out, lse, B, S, H, D, scale, p, seed, salt, 0, nullptr, 0, 0, st);
+}
+
+// dqkv [B*S][3*H*D] fully overwritten (dQ | dK | dV); out = the forward's output; dot
+// [B*H*S] fp32 scratch.
+MLC_EXPORT int mlc_flash_bwd(const bf16* qkv, const float* key_bias, const bf16* out, const bf16* dout,
+                             const float* lse, float* dot, bf16* dqkv, int B, int S, int H, int D, float scale,
+                             float p, const uint32_t* seed, uint32_t salt, hipStream_t st) {
+  return flash_bwd(qkv, key_bias, out, dout, lse, dot, dqkv, B, S, H, D, scale, p, seed, salt, 0, nullptr, 0, 0, st);
+}
+
+// The same with attention masks: softmax(scale * Q K^T + key_bias + attn_bias [+ causal]).
+// causal != 0: query q sees keys <= q (a query block streams only the key tiles up to its
+// diagonal).  attn_bias (may be null): fp32, element (b, h, q, key) at
+// attn_bias[b * stride_b + h * stride_h + q * S + key], a stride of 0 broadcasts; values finite
+// or -inf.  A fully masked row gives zero output, lse = +inf and zero gradients.  Masked calls
+// always run the streaming kernels (also at S = 128, D = 64).
+MLC_EXPORT int mlc_flash_fwd_masked(const bf16* qkv, const float* key_bias, bf16* out, float* lse, int B, int S,
+                                    int H, int D, float scale, float p, const uint32_t* seed, uint32_t salt,
+                                    int causal, const float* attn_bias, long stride_b, long stride_h,
+                                    hipStream_t st) {
+  return flash_fwd(qkv, key_bias, out, lse, B, S, H, D, scale, p, seed, salt, causal, attn_bias, stride_b, stride_h,
+                   st);
+}
+
+MLC_EXPORT int mlc_flash_bwd_masked(const bf16* qkv, const float* key_bias, const bf16* out, const bf16* dout,
+                                    const float* lse, float* dot, bf16* dqkv, int B, int S, int H, int D,
+                                    float scale, float p, const uint32_t* seed, uint32_t salt, int causal,
+                                    const float* attn_bias, long stride_b, long stride_h, hipStream_t st) {
+  return flash_bwd(qkv, key_bias, out, dout, lse, dot, dqkv, B, S, H, D, scale, p, seed, salt, causal, attn_bias,
+                   stride_b, stride_h, st);
 }
 
 // A/B knob of the S = 128 fused backward: value 0 / 1 sets it, < 0 only reads; returns the

@@ -557,16 +557,24 @@ class _Lowering:
         q = a.get('query')
         if a.get('key') is not q or a.get('value') is not q:
             raise NativeUnsupported(f'{node.target}: MultiheadAttention lowers for self-attention only (q = k = v)')
-        if a.get('attn_mask') is not None or a.get('is_causal'):
-            raise NativeUnsupported(f'{node.target}: MultiheadAttention attn_mask / is_causal (native: a key-padding '
-                                    'mask only)')
+        causal, mask = a.get('is_causal', False), a.get('attn_mask')
+        if isinstance(causal, fx.Node):
+            raise NativeUnsupported(f'{node.target}: MultiheadAttention with a traced is_causal (native: a literal)')
+        if causal and mask is None:         # torch's own rule: the hint describes the mask that is passed
+            raise NativeUnsupported(f'{node.target}: MultiheadAttention is_causal=True without an attn_mask')
+        if mask is not None and not isinstance(mask, fx.Node):
+            raise NativeUnsupported(f'{node.target}: MultiheadAttention attn_mask {type(mask).__name__} (native: a '
+                                    'tensor)')
+        if causal:
+            mask = None                     # the causal mode of the kernels; the mask tensor is not read
         users = self._getitem_users(node)
         if users is None or any(u.users for i, us in users.items() if i != 0 for u in us):
             raise NativeUnsupported(f'{node.target}: MultiheadAttention attention weights are used (native: the '
                                     'output only)')
         kpm = a.get('key_padding_mask')
-        site = GT.MHASite(self.net.ctx, self.net.mha_params(node.target, m))
-        new = self._site_node(node, site, [q] + ([kpm] if kpm is not None else []))
+        site = GT.MHASite(self.net.ctx, self.net.mha_params(node.target, m), causal=bool(causal),
+                          has_mask=mask is not None)
+        new = self._site_node(node, site, [q] + [t for t in (kpm, mask) if t is not None])
         for i, us in users.items():
             for u in us:
                 if i == 0:
@@ -630,26 +638,35 @@ class _Lowering:
     def sdpa(self, node):
         a = self._call_args(node, ('query', 'key', 'value', 'attn_mask', 'dropout_p', 'is_causal', 'scale',
                                    'enable_gqa'))
-        if a.get('attn_mask') is not None or a.get('is_causal') or a.get('enable_gqa'):
-            raise NativeUnsupported(f'{node.name}: scaled_dot_product_attention with a mask / is_causal / GQA '
-                                    '(native: unmasked self-attention)')
+        if a.get('enable_gqa'):
+            raise NativeUnsupported(f'{node.name}: scaled_dot_product_attention with enable_gqa (native: as many '
+                                    'key / value heads as query heads)')
         p, scale = a.get('dropout_p', 0.0), a.get('scale')
-        if isinstance(p, fx.Node) or isinstance(scale, fx.Node):
-            raise NativeUnsupported(f'{node.name}: scaled_dot_product_attention with a traced dropout_p / scale')
+        causal, mask = a.get('is_causal', False), a.get('attn_mask')
+        if isinstance(p, fx.Node) or isinstance(scale, fx.Node) or isinstance(causal, fx.Node):
+            raise NativeUnsupported(f'{node.name}: scaled_dot_product_attention with a traced dropout_p / scale / '
+                                    'is_causal')
+        if mask is not None and not isinstance(mask, fx.Node):
+            raise NativeUnsupported(f'{node.name}: scaled_dot_product_attention attn_mask {type(mask).__name__} '
+                                    '(native: a tensor)')
+        if causal and mask is not None:     # torch raises for this pair too
+            raise NativeUnsupported(f'{node.name}: scaled_dot_product_attention with both attn_mask and is_causal')
+        kw = dict(causal=bool(causal), has_mask=mask is not None)
+        extra = [mask] if mask is not None else []
         packed = self._packed_qkv(a['query'], a['key'], a['value'])
         if packed is not None and all(len(n.users) == 1 for n in packed[2][:3]):
             # zero-copy: the projection's [B, N, 3E] output IS the kernel's qkv layout
             L, H, chain = packed
-            site = GT.SDPASite(self.net.ctx, float(p or 0.0), None if scale is None else float(scale), heads=H)
-            new = self._site_node(node, site, [L])
+            site = GT.SDPASite(self.net.ctx, float(p or 0.0), None if scale is None else float(scale), heads=H, **kw)
+            new = self._site_node(node, site, [L] + extra)
             self._replace([node], new)
             for n in chain:
                 if not n.users and n not in self.erased:
                     self.gm.graph.erase_node(n)
                     self.erased.add(n)
             return
-        site = GT.SDPASite(self.net.ctx, float(p or 0.0), None if scale is None else float(scale))
-        new = self._site_node(node, site, [a['query'], a['key'], a['value']])
+        site = GT.SDPASite(self.net.ctx, float(p or 0.0), None if scale is None else float(scale), **kw)
+        new = self._site_node(node, site, [a['query'], a['key'], a['value']] + extra)
         self._replace([node], new)
 
     def patch_embed(self, node, m):

@@ -10,15 +10,17 @@ these sites reach them from a torch.fx graph of ANY model:
   LayerNorm forward / backward (the residual add fused into the normalisation pass);
 * ``nn.MultiheadAttention`` (self-attention)   -> :class:`MHASite`: packed in-projection GEMM,
   the fused flash attention (``flash_attn.hip``, any S, head dim <= 128, key-padding
-  mask as a key bias), out-projection GEMM;
+  mask as a key bias, ``attn_mask`` / ``is_causal`` as the kernels' mask modes),
+  out-projection GEMM;
 * ``nn.TransformerEncoderLayer`` / ``nn.TransformerEncoder`` -> :class:`EncoderSite`: the
   whole layer as one autograd node (post-norm or pre-norm, ReLU or exact GELU, all three
   dropouts on the kernels' counter-hash masks), scheduled like the hand BERT engine:
   dropout + residual fused into the LayerNorm passes, GELU'(pre-activation) stored by the
   FFN GEMM epilogue and multiplied in the next input-gradient epilogue, weight gradients
   on the side stream;
-* ``F.scaled_dot_product_attention`` (no mask, not causal) -> :class:`SDPASite`: q/k/v packed
-  into the kernel's [B*S, 3*H*D] layout, flash attention forward / backward;
+* ``F.scaled_dot_product_attention`` (also ``is_causal=True`` / ``attn_mask=``) ->
+  :class:`SDPASite`: q/k/v packed into the kernel's [B*S, 3*H*D] layout, flash attention
+  forward / backward (causal tile skipping, additive mask as a second bias operand);
 * ``Linear -> GELU`` -> a dense GEMM with the GELU in its epilogue (:class:`LinearGelu`).
 
 Every GEMM is the framework's own MFMA kernel (``igemm.hip`` dense epilogues): no hipBLASLt,
@@ -252,13 +254,14 @@ class _Attn:
     def p_now(self):
         return self.p if self.ctx.training else 0.0
 
-    def fwd(self, qkv, kb, B, S):
+    def fwd(self, qkv, kb, B, S, causal=False, attn_bias=None):
         return Tx.attn_fwd(qkv, kb, B, S, self.H, self.scale, self.p_now(), _seed(self.ctx), self.salt,
-                           head_dim=self.D)
+                           head_dim=self.D, causal=causal, attn_bias=attn_bias)
 
-    def bwd(self, qkv, kb, dctx, lse, ctx2, B, S):
+    def bwd(self, qkv, kb, dctx, lse, ctx2, B, S, causal=False, attn_bias=None):
         return Tx.attn_bwd(qkv, kb, dctx.contiguous(), lse, B, S, self.H, self.scale, self.p_now(),
-                           _seed(self.ctx), self.salt, head_dim=self.D, ctx=ctx2)
+                           _seed(self.ctx), self.salt, head_dim=self.D, ctx=ctx2, causal=causal,
+                           attn_bias=attn_bias)
 
 
 def key_bias_of(mask: Optional[torch.Tensor], B: int, S: int) -> Optional[torch.Tensor]:
@@ -271,6 +274,17 @@ def key_bias_of(mask: Optional[torch.Tensor], B: int, S: int) -> Optional[torch.
     else:
         kb = mask.float()
     return kb.contiguous()
+
+
+def additive_mask(mask: torch.Tensor, true_masks_out: bool) -> torch.Tensor:
+    """An attention mask -> the kernels' additive fp32 bias.  A float mask is added as it is.
+    A bool mask becomes 0 / -inf with the caller's polarity: ``nn.MultiheadAttention`` masks
+    out where True, ``F.scaled_dot_product_attention`` takes part where True.  No value is
+    inspected (that would synchronise, and the step is captured in a graph)."""
+    if mask.dtype != torch.bool:
+        return mask.float()
+    out = mask if true_masks_out else ~mask
+    return torch.zeros(mask.shape, device=mask.device, dtype=torch.float32).masked_fill(out, float('-inf'))
 
 
 def mha_supported(m: nn.MultiheadAttention) -> Optional[str]:
@@ -300,23 +314,29 @@ class MHAParams:
 
 
 class MHASite(Site):
-    """Self-attention ``mha(x, x, x, key_padding_mask=...)[0]``: in-projection GEMM, flash
-    attention, out-projection GEMM.  Sequence-first inputs ([S, B, E]) are transposed to
-    batch-first rows on the way in and viewed back on the way out."""
+    """Self-attention ``mha(x, x, x, key_padding_mask=..., attn_mask=..., is_causal=...)[0]``:
+    in-projection GEMM, flash attention, out-projection GEMM.  Sequence-first inputs
+    ([S, B, E]) are transposed to batch-first rows on the way in and viewed back on the way
+    out.  ``causal``: the call had a literal ``is_causal=True`` (the mask tensor is then not
+    read).  ``has_mask``: the last input is ``attn_mask`` ([S, S] or [B*H, S, S]; bool True =
+    masked out, float added), a constant: no gradient is returned for it."""
 
-    def __init__(self, ctx, mp: MHAParams):
+    def __init__(self, ctx, mp: MHAParams, causal: bool = False, has_mask: bool = False):
         super().__init__(ctx)
         object.__setattr__(self, 'mp', mp)
         object.__setattr__(self, 'attn', _Attn(ctx, mp.heads, mp.E, mp.p))
+        self.causal, self.has_mask = bool(causal), bool(has_mask)
 
     def params(self):
         return [self.mp.inp, self.mp.out]
 
-    def forward(self, x, kpm=None):
-        return _run(self, x, kpm) if kpm is not None else _run(self, x)
+    def forward(self, x, *masks):
+        return _run(self, x, *masks)
 
-    def fwd(self, x, kpm=None):
+    def fwd(self, x, *masks):
         mp = self.mp
+        mask = masks[-1] if self.has_mask else None
+        kpm = masks[0] if len(masks) > int(self.has_mask) else None
         if mp.batch_first:
             B, S, E = x.shape
             x2 = _rows(x)
@@ -324,30 +344,35 @@ class MHASite(Site):
             S, B, E = x.shape
             x2 = _rows(x.transpose(0, 1))
         kb = key_bias_of(kpm, B, S)
+        ab = None
+        if mask is not None:
+            if tuple(mask.shape) not in ((S, S), (B * mp.heads, S, S)):
+                raise ValueError(f'MultiheadAttention attn_mask shape {tuple(mask.shape)}: expected '
+                                 f'({S}, {S}) or ({B * mp.heads}, {S}, {S})')
+            ab = Tx.attn_bias_arg(additive_mask(mask, true_masks_out=True), B, S, mp.heads)[0]
         qkv, _ = mp.inp.fwd(x2)
-        ctx2, lse = self.attn.fwd(qkv, kb, B, S)
+        ctx2, lse = self.attn.fwd(qkv, kb, B, S, self.causal, ab)
         out, _ = mp.out.fwd(ctx2)
         y = out.view(B, S, E)
         if not mp.batch_first:
             y = y.transpose(0, 1)
-        saved = [x2, qkv, lse, ctx2] + ([kb] if kb is not None else [])
-        return y, saved, (B, S, x.dtype, kb is not None)
+        saved = [x2, qkv, lse, ctx2] + ([kb] if kb is not None else []) + ([ab] if ab is not None else [])
+        return y, saved, (B, S, x.dtype, kb is not None, ab is not None)
 
     def bwd(self, dout, saved, keep, needs):
         mp = self.mp
-        B, S, xdt, has_kb = keep
+        B, S, xdt, has_kb, has_ab = keep
         x2, qkv, lse, ctx2 = saved[:4]
         kb = saved[4] if has_kb else None
+        ab = saved[-1] if has_ab else None
         d = dout if mp.batch_first else dout.transpose(0, 1)
         dctx = mp.out.backward(_rows(d), ctx2)
-        dqkv = self.attn.bwd(qkv, kb, dctx, lse, ctx2, B, S)
+        dqkv = self.attn.bwd(qkv, kb, dctx, lse, ctx2, B, S, self.causal, ab)
         dx = mp.inp.backward(dqkv, x2, need_dx=needs[0])
-        out = [None]
+        out = [None] * len(needs)         # the masks are constants
         if dx is not None:
             dx = dx.view(B, S, -1)
             out[0] = (dx if mp.batch_first else dx.transpose(0, 1)).to(xdt)
-        if len(needs) > 1:
-            out.append(None)
         return out
 
 
@@ -546,7 +571,7 @@ class EncoderSite(nn.Module):
 
 # ---------------------------------------------------------------------------- SDPA, dense + GELU
 class SDPASite(Site):
-    """``F.scaled_dot_product_attention(q, k, v, dropout_p=p, scale=s)`` (no mask, not causal)
+    """``F.scaled_dot_product_attention(q, k, v, attn_mask=m, dropout_p=p, is_causal=c, scale=s)``
     on the flash kernels; the output is a [B, H, S, D] view of the kernel's [B*S, H*D]
     context rows (so a following ``transpose(1, 2).reshape(B, S, H*D)`` is free).
 
@@ -554,12 +579,31 @@ class SDPASite(Site):
     3, 1, 4)`` split): the single input is the projection output [B, N, 3*H*D], which already
     is the kernel's packed layout - no copy forward, and the packed gradient is the
     projection's output gradient - no copy backward.  Otherwise q / k / v [B, H, S, D] are
-    packed with one copy."""
+    packed with one copy.
 
-    def __init__(self, ctx, p: float = 0.0, scale: Optional[float] = None, heads: Optional[int] = None):
+    ``causal``: a literal ``is_causal=True``.  ``has_mask``: the last input is ``attn_mask``
+    (bool True = takes part, float added): [S, S] or [B|1, H|1, S, S] become the kernels'
+    additive bias, [B, 1, 1, S] the key bias.  Masks are constants: no gradient is returned."""
+
+    def __init__(self, ctx, p: float = 0.0, scale: Optional[float] = None, heads: Optional[int] = None,
+                 causal: bool = False, has_mask: bool = False):
         super().__init__(ctx)
         self.p, self.scale, self.heads = float(p), scale, heads
+        self.causal, self.has_mask = bool(causal), bool(has_mask)
         self.salt = next_salt(ctx)
+
+    @staticmethod
+    def _masks(mask, B, H, S):
+        """attn_mask -> (key bias [B, S] or None, additive bias [b, h, S, S] or None)."""
+        shape = tuple(mask.shape)
+        add = additive_mask(mask, true_masks_out=False)
+        if shape == (B, 1, 1, S) and S > 1:
+            return add.reshape(B, S).contiguous(), None
+        if shape == (S, S) or (len(shape) == 4 and shape[0] in (1, B) and shape[1] in (1, H)
+                               and shape[2:] == (S, S)):
+            return None, Tx.attn_bias_arg(add, B, S, H)[0]
+        raise ValueError(f'SDPA site: attn_mask shape {shape} (native: ({S}, {S}), ({B}|1, {H}|1, {S}, {S}) or '
+                         f'({B}, 1, 1, {S}))')
 
     def params(self):
         return []
@@ -568,6 +612,9 @@ class SDPASite(Site):
         return _run(self, *qkv)
 
     def fwd(self, *inputs):
+        mask = None
+        if self.has_mask:
+            inputs, mask = inputs[:-1], inputs[-1]
         if self.heads is not None:
             (L,) = inputs
             B, S, E3 = L.shape
@@ -586,22 +633,28 @@ class SDPASite(Site):
             dt = q.dtype
         scale = self.scale if self.scale is not None else 1.0 / math.sqrt(D)
         p = self.p if self.ctx.training else 0.0
-        ctx2, lse = Tx.attn_fwd(qkv, None, B, S, H, scale, p, _seed(self.ctx), self.salt, head_dim=D)
+        kb, ab = self._masks(mask, B, H, S) if mask is not None else (None, None)
+        ctx2, lse = Tx.attn_fwd(qkv, kb, B, S, H, scale, p, _seed(self.ctx), self.salt, head_dim=D,
+                                causal=self.causal, attn_bias=ab)
         out = ctx2.view(B, S, H, D).transpose(1, 2)
-        return out, [qkv, lse, ctx2], (B, H, S, D, scale, p, dt)
+        saved = [qkv, lse, ctx2] + [t for t in (kb, ab) if t is not None]
+        return out, saved, (B, H, S, D, scale, p, dt, kb is not None, ab is not None)
 
     def bwd(self, dout, saved, keep, needs):
-        qkv, lse, ctx2 = saved
-        B, H, S, D, scale, p, dt = keep
+        qkv, lse, ctx2 = saved[:3]
+        B, H, S, D, scale, p, dt, has_kb, has_ab = keep
+        kb = saved[3] if has_kb else None
+        ab = saved[-1] if has_ab else None
+        none = [None] * int(self.has_mask)       # the mask is a constant
         dctx = dout.transpose(1, 2).reshape(B * S, H * D)
         if dctx.dtype != torch.bfloat16:
             dctx = dctx.to(torch.bfloat16)
-        dqkv = Tx.attn_bwd(qkv, None, dctx.contiguous(), lse, B, S, H, scale, p, _seed(self.ctx), self.salt,
-                           head_dim=D, ctx=ctx2)
+        dqkv = Tx.attn_bwd(qkv, kb, dctx.contiguous(), lse, B, S, H, scale, p, _seed(self.ctx), self.salt,
+                           head_dim=D, ctx=ctx2, causal=self.causal, attn_bias=ab)
         if self.heads is not None:
-            return [dqkv.view(B, S, 3 * H * D).to(dt) if needs[0] else None]
+            return [dqkv.view(B, S, 3 * H * D).to(dt) if needs[0] else None] + none
         d = dqkv.view(B, S, 3, H, D).permute(2, 0, 3, 1, 4)                   # [3, B, H, S, D]
-        return [d[i].to(dt) if needs[i] else None for i in range(3)]
+        return [d[i].to(dt) if needs[i] else None for i in range(3)] + none
 
 
 class PatchEmbed(Site):
@@ -736,4 +789,4 @@ class LinearGelu(Site):
 
 
 __all__ = ['DenseSet', 'LNParams', 'LayerNormSite', 'MHAParams', 'MHASite', 'EncoderLayerParams', 'EncoderSite',
-           'SDPASite', 'LinearGelu', 'PatchEmbed', 'MlpSite', 'dense_backward', 'encoder_layer_supported', 'mha_supported', 'key_bias_of', 'next_salt']
+           'SDPASite', 'LinearGelu', 'PatchEmbed', 'MlpSite', 'dense_backward', 'encoder_layer_supported', 'mha_supported', 'key_bias_of', 'additive_mask', 'next_salt']

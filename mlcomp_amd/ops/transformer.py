@@ -249,68 +249,124 @@ def _unpad_heads(t, rows, groups, H, D, Dp):
     return t.view(rows, groups, H, Dp)[..., :D].reshape(rows, groups * H * D)
 
 
-def _attn_ref_probs(qkv, key_bias, B, S, H, scale, D=64):
-    E = H * D
+def attn_bias_arg(attn_bias, B: int, S: int, H: int):
+    """An additive attention mask -> (contiguous fp32 tensor, batch stride, head stride) as
+    the kernels read it: element (b, h, q, key) at ``b*stride_b + h*stride_h + q*S + key``.
+    Accepted shapes: [S, S]; [B, H, S, S] where size-1 dims broadcast (stride 0); [B*H, S, S]."""
+    if attn_bias is None:
+        return None, 0, 0
+    shape = tuple(attn_bias.shape)
+    if attn_bias.dtype == torch.bool:
+        raise ValueError('attn_bias is additive (float); turn a bool mask into 0 / -inf first')
+    if shape == (S, S):
+        b, h = 1, 1
+    elif len(shape) == 3 and shape == (B * H, S, S):
+        b, h = B, H
+    elif len(shape) == 4 and shape[2:] == (S, S) and shape[0] in (1, B) and shape[1] in (1, H):
+        b, h = shape[:2]
+    else:
+        raise ValueError(f'attn_bias shape {shape}: expected [S, S], [B|1, H|1, S, S] or [B*H, S, S] with '
+                         f'B={B}, H={H}, S={S}')
+    t = attn_bias.reshape(b, h, S, S)
+    if t.dtype != torch.float32:
+        t = t.float()
+    t = t.contiguous()
+    return t, (h * S * S if b > 1 else 0), (S * S if h > 1 else 0)
+
+
+def _attn_ref_scores(qkv, key_bias, B, S, H, scale, D=64, causal=False, attn_bias=None):
     q, k, v = qkv.float().view(B, S, 3, H, D).permute(2, 0, 3, 1, 4).unbind(0)   # [B, H, S, D]
     x = torch.matmul(q, k.transpose(-1, -2)) * scale
     if key_bias is not None:
         x = x + key_bias.float()[:, None, None, :]
-    P = torch.softmax(x, -1).nan_to_num(0.0)
-    return q, k, v, P, E
+    if attn_bias is not None:
+        x = x + attn_bias_arg(attn_bias, B, S, H)[0]
+    if causal:
+        x = x.masked_fill(torch.ones(S, S, dtype=torch.bool, device=x.device).triu(1), float('-inf'))
+    return q, k, v, x
 
 
-def attn_fwd(qkv, key_bias, B, S, H, scale, p=0.0, seed=None, salt=0, head_dim: int = 64):
+def _attn_ref_probs(qkv, key_bias, B, S, H, scale, D=64, causal=False, attn_bias=None):
+    q, k, v, x = _attn_ref_scores(qkv, key_bias, B, S, H, scale, D, causal, attn_bias)
+    P = torch.softmax(x, -1).nan_to_num(0.0)     # a fully masked row: all zeros
+    return q, k, v, P, H * D
+
+
+def attn_fwd(qkv, key_bias, B, S, H, scale, p=0.0, seed=None, salt=0, head_dim: int = 64, *, causal: bool = False,
+             attn_bias=None):
     """Fused multi-head attention over the QKV projection output ``qkv`` [B*S, 3*H*D]
     (columns q | k | v, head h at h*D).  Returns (ctx [B*S, H*D] bf16, lse [B*H*S] fp32).
     Attention-probability dropout uses the softmax kernel's mask indexing
-    (((b*H + h)*S + q)*S + key), so every path drops the same elements."""
+    (((b*H + h)*S + q)*S + key), so every path drops the same elements.
+    ``causal``: query q attends to keys <= q.  ``attn_bias``: an additive float mask ([S, S],
+    [B|1, H|1, S, S] or [B*H, S, S]; finite or -inf) summed with the scaled scores; both
+    compose with ``key_bias`` and dropout and always run the streaming kernels.  A fully
+    masked row gives zero context and lse = +inf."""
     D = head_dim
+    masked = bool(causal) or attn_bias is not None
     if _cuda(qkv) and D not in (64, 128):
         assert attn_supported(S, D), (S, D)
         Dp = _pad_dim(D)
-        ctx, lse = attn_fwd(_pad_heads(qkv, B * S, 3, H, D, Dp), key_bias, B, S, H, scale, p, seed, salt, Dp)
+        ctx, lse = attn_fwd(_pad_heads(qkv, B * S, 3, H, D, Dp), key_bias, B, S, H, scale, p, seed, salt, Dp,
+                            causal=causal, attn_bias=attn_bias)
         return _unpad_heads(ctx, B * S, 1, H, D, Dp), lse
     if _cuda(qkv):
         assert attn_supported(S, D) and qkv.is_contiguous() and tuple(qkv.shape) == (B * S, 3 * H * D)
         assert key_bias is None or (key_bias.is_contiguous() and tuple(key_bias.shape) == (B, S))
         ctx = torch.empty(B * S, H * D, device=qkv.device, dtype=torch.bfloat16)
         lse = torch.empty(B * H * S, device=qkv.device, dtype=torch.float32)
-        if _attn_small(S, D):
+        if masked:
+            ab, sb, sh = attn_bias_arg(attn_bias, B, S, H)
+            _lib.call('mlc_flash_fwd_masked', _lib.ptr(qkv), _lib.ptr(key_bias), _lib.ptr(ctx), _lib.ptr(lse), B, S,
+                      H, D, float(scale), float(p), _lib.ptr(seed), salt, int(bool(causal)), _lib.ptr(ab), sb, sh,
+                      _lib.stream())
+        elif _attn_small(S, D):
             _lib.call('mlc_attn_fwd', _lib.ptr(qkv), _lib.ptr(key_bias), _lib.ptr(ctx), _lib.ptr(lse), B, S, H,
                       float(scale), float(p), _lib.ptr(seed), salt, _lib.stream())
         else:
             _lib.call('mlc_flash_fwd', _lib.ptr(qkv), _lib.ptr(key_bias), _lib.ptr(ctx), _lib.ptr(lse), B, S, H, D,
                       float(scale), float(p), _lib.ptr(seed), salt, _lib.stream())
         return ctx, lse
-    q, k, v, P, E = _attn_ref_probs(qkv, key_bias, B, S, H, scale, D)
+    q, k, v, x = _attn_ref_scores(qkv, key_bias, B, S, H, scale, D, causal, attn_bias)
+    P = torch.softmax(x, -1).nan_to_num(0.0)
     Pd = P
     if p > 0:
         m = keep_mask((B, H, S, S), p, _seed_val(seed), salt)
         Pd = torch.where(m, P / (1 - p), torch.zeros_like(P))
-    ctx = torch.matmul(Pd, v).permute(0, 2, 1, 3).reshape(B * S, E)
-    x = torch.matmul(q, k.transpose(-1, -2)) * scale
-    if key_bias is not None:
-        x = x + key_bias.float()[:, None, None, :]
+    ctx = torch.matmul(Pd, v).permute(0, 2, 1, 3).reshape(B * S, H * D)
     lse = torch.logsumexp(x, -1).reshape(-1)
+    if masked:
+        lse = torch.where(lse == float('-inf'), torch.full_like(lse, float('inf')), lse)   # the kernels' +inf
     return ctx.to(torch.bfloat16), lse
 
 
-def attn_bwd(qkv, key_bias, dctx, lse, B, S, H, scale, p=0.0, seed=None, salt=0, head_dim: int = 64, ctx=None):
+def attn_bwd(qkv, key_bias, dctx, lse, B, S, H, scale, p=0.0, seed=None, salt=0, head_dim: int = 64, ctx=None, *,
+             causal: bool = False, attn_bias=None):
     """Gradient of :func:`attn_fwd` wrt ``qkv``: returns dqkv [B*S, 3*H*D] bf16.  ``ctx``
-    (the forward output) is needed by the streaming kernels (rowsum(dO * O))."""
+    (the forward output) is needed by the streaming kernels (rowsum(dO * O)).  ``causal`` /
+    ``attn_bias`` as in the forward; masks are constants (no gradient)."""
     D = head_dim
+    masked = bool(causal) or attn_bias is not None
     if _cuda(qkv) and D not in (64, 128):
         assert attn_supported(S, D) and ctx is not None, (S, D)
         Dp = _pad_dim(D)
         dq = attn_bwd(_pad_heads(qkv, B * S, 3, H, D, Dp), key_bias, _pad_heads(dctx, B * S, 1, H, D, Dp), lse,
-                      B, S, H, scale, p, seed, salt, Dp, ctx=_pad_heads(ctx, B * S, 1, H, D, Dp))
+                      B, S, H, scale, p, seed, salt, Dp, ctx=_pad_heads(ctx, B * S, 1, H, D, Dp), causal=causal,
+                      attn_bias=attn_bias)
         return _unpad_heads(dq, B * S, 3, H, D, Dp)
     if _cuda(qkv):
         assert attn_supported(S, D) and qkv.is_contiguous() and tuple(qkv.shape) == (B * S, 3 * H * D)
         assert dctx.is_contiguous() and tuple(dctx.shape) == (B * S, H * D) and lse.numel() == B * H * S
         assert key_bias is None or (key_bias.is_contiguous() and tuple(key_bias.shape) == (B, S))
         dqkv = torch.empty_like(qkv)
-        if _attn_small(S, D):
+        if masked:
+            assert ctx is not None and ctx.is_contiguous() and ctx.shape == dctx.shape
+            ab, sb, sh = attn_bias_arg(attn_bias, B, S, H)
+            dot = torch.empty(B * H * S, device=qkv.device, dtype=torch.float32)
+            _lib.call('mlc_flash_bwd_masked', _lib.ptr(qkv), _lib.ptr(key_bias), _lib.ptr(ctx), _lib.ptr(dctx),
+                      _lib.ptr(lse), _lib.ptr(dot), _lib.ptr(dqkv), B, S, H, D, float(scale), float(p),
+                      _lib.ptr(seed), salt, int(bool(causal)), _lib.ptr(ab), sb, sh, _lib.stream())
+        elif _attn_small(S, D):
             _lib.call('mlc_attn_bwd', _lib.ptr(qkv), _lib.ptr(key_bias), _lib.ptr(dctx), _lib.ptr(lse),
                       _lib.ptr(dqkv), B, S, H, float(scale), float(p), _lib.ptr(seed), salt, _lib.stream())
         else:
@@ -320,7 +376,7 @@ def attn_bwd(qkv, key_bias, dctx, lse, B, S, H, scale, p=0.0, seed=None, salt=0,
                       _lib.ptr(lse), _lib.ptr(dot), _lib.ptr(dqkv), B, S, H, D, float(scale), float(p),
                       _lib.ptr(seed), salt, _lib.stream())
         return dqkv
-    q, k, v, P, E = _attn_ref_probs(qkv, key_bias, B, S, H, scale, D)
+    q, k, v, P, E = _attn_ref_probs(qkv, key_bias, B, S, H, scale, D, causal, attn_bias)
     do = dctx.float().view(B, S, H, D).permute(0, 2, 1, 3)
     m = keep_mask((B, H, S, S), p, _seed_val(seed), salt) if p > 0 else None
     Pd = torch.where(m, P / (1 - p), torch.zeros_like(P)) if m is not None else P
