@@ -1457,6 +1457,29 @@ static int g_persist_kt = 8;
 static int g_persist_nbuf = 3;
 static int g_num_cus = 0;
 
+// MLC_GEMM_PERSIST* environment defaults and the CU count, read once on first use
+static void resolve_persist_defaults() {
+  if (g_persist >= 0) return;
+  const char* e = getenv("MLC_GEMM_PERSIST");
+  g_persist = e ? atoi(e) : 0;
+  if (const char* k = getenv("MLC_GEMM_PERSIST_KT")) g_persist_kt = atoi(k);
+  if (const char* b = getenv("MLC_GEMM_PERSIST_NBUF")) g_persist_nbuf = atoi(b);
+  int dev = 0;
+  hipGetDevice(&dev);
+  hipDeviceGetAttribute(&g_num_cus, hipDeviceAttributeMultiprocessorCount, dev);
+  if (g_num_cus <= 0) g_num_cus = 256;
+}
+
+// Round a split-K factor so that no split is empty (what the launch runs, and so how many
+// slabs a reduction pass has to sum); *per: K-tiles of one split, 0 for an empty K.
+static int round_splits(int ktiles, int splits, int* per = nullptr) {
+  if (splits < 1) splits = 1;
+  if (splits > ktiles) splits = ktiles > 0 ? ktiles : 1;
+  const int p = ktiles > 0 ? (ktiles + splits - 1) / splits : 0;
+  if (per) *per = p;
+  return p > 0 ? (ktiles + p - 1) / p : 1;
+}
+
 template <class EPI>
 static bool epi_loads(const EPI& e) {
   if constexpr (IsEpiBF16<EPI>::value) return e.addend || e.bn.y0 || e.dact || e.bias || e.preact;
@@ -1469,16 +1492,7 @@ static hipError_t launch(const LA& la, const LB& lb, const EPI& epi, int M, int 
   const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
   const int ktiles = (K + BK - 1) / BK;
   if constexpr (BM == 128 && BN == 128 && HasDma<LA>::value && HasDma<LB>::value && IsEpiBF16<EPI>::value) {
-    if (g_persist < 0) {
-      const char* e = getenv("MLC_GEMM_PERSIST");
-      g_persist = e ? atoi(e) : 0;
-      if (const char* k = getenv("MLC_GEMM_PERSIST_KT")) g_persist_kt = atoi(k);
-      if (const char* b = getenv("MLC_GEMM_PERSIST_NBUF")) g_persist_nbuf = atoi(b);
-      int dev = 0;
-      hipGetDevice(&dev);
-      hipDeviceGetAttribute(&g_num_cus, hipDeviceAttributeMultiprocessorCount, dev);
-      if (g_num_cus <= 0) g_num_cus = 256;
-    }
+    resolve_persist_defaults();
     if (g_persist && splits <= 1 && ktiles >= 1 && ktiles <= g_persist_kt && tiles >= 2 * g_num_cus &&
         (g_persist >= 2 || !epi_loads(epi))) {
       const int grid = g_num_cus;            // one block per CU (the LDS ring + staging region)
@@ -1491,10 +1505,8 @@ static hipError_t launch(const LA& la, const LB& lb, const EPI& epi, int M, int 
       return hipGetLastError();
     }
   }
-  if (splits < 1) splits = 1;
-  if (splits > ktiles) splits = ktiles > 0 ? ktiles : 1;
-  const int per = ktiles > 0 ? (ktiles + splits - 1) / splits : 0;
-  splits = per > 0 ? (ktiles + per - 1) / per : 1;
+  int per;
+  splits = round_splits(ktiles, splits, &per);
   dim3 grid(tiles, 1, splits);
   if (per <= (g_single_stage_kt > 1 ? g_single_stage_kt : 1) && g_single_stage) {
     hipLaunchKernelGGL((gemm_kernel<BM, BN, LA, LB, EPI, 0>), grid, dim3(NTHR), 0, st, la, lb, epi, M, N, K, per);
@@ -1730,18 +1742,91 @@ static int auto_splits(int M, int N, int K, int tile, int target = g_split_targe
 using namespace igemm;
 using namespace igemm_host;
 
+// Loader factories: the host code describes an operand once and make<R>() builds its loader
+// for an R-row tile, so a runtime tile id can pick the template arguments (launch_tiles).
+struct MkMatKC {
+  const bf16* p; int ld, rows, K;
+  template <int R> MatKC<R> make() const { return MatKC<R>{p, ld, rows, K}; }
+};
+struct MkMatMC {
+  const bf16* p; int ld, K, cols;
+  template <int R> MatMC<R> make() const { return MatMC<R>{p, ld, K, cols}; }
+};
+struct MkMatMCSum {
+  const bf16* p; int ld, K, cols; float* colsum;
+  template <int R> MatMCSum<R> make() const { return MatMCSum<R>{p, ld, K, cols, colsum}; }
+};
+struct MkMatKCBn {
+  const bf16* p; int ld, rows, K; BnIn bn;
+  template <int R> MatKCBn<R> make() const { return MatKCBn<R>{{p, ld, rows, K}, bn}; }
+};
+struct MkMatMCBn {
+  const bf16* p; int ld, K, cols; BnIn bn;
+  template <int R> MatMCBn<R> make() const { return MatMCBn<R>{{p, ld, K, cols}, bn}; }
+};
+struct MkConvFwdA {
+  const bf16* x; ConvGeom g; int M, K;
+  template <int R> ConvFwdA<R> make() const { return ConvFwdA<R>{x, g, M, K}; }
+};
+struct MkConvFwdABn {
+  const bf16* x; ConvGeom g; int M, K; BnIn bn;
+  template <int R> ConvFwdABn<R> make() const { return ConvFwdABn<R>{{x, g, M, K}, bn}; }
+};
+struct MkConvDgradA {
+  const bf16* dy; ConvGeom g; int M, K; DgradClass cl;
+  template <int R> ConvDgradA<R> make() const { return ConvDgradA<R>{dy, g, M, K, cl}; }
+};
+struct MkConvDgradB {
+  const bf16* w; ConvGeom g; DgradClass cl;
+  template <int R> ConvDgradB<R> make() const { return ConvDgradB<R>{w, g, cl}; }
+};
+struct MkConvDgradBT {
+  const bf16* wt; ConvGeom g; DgradClass cl;
+  template <int R> ConvDgradBT<R> make() const { return ConvDgradBT<R>{wt, g, cl}; }
+};
+struct MkConvWgradB {
+  const bf16* x; ConvGeom g; int P, KK;
+  template <int R> ConvWgradB<R> make() const { return ConvWgradB<R>{x, g, P, KK}; }
+};
+struct MkConvWgradBBn {
+  const bf16* x; ConvGeom g; int P, KK; BnIn bn;
+  template <int R> ConvWgradBBn<R> make() const { return ConvWgradBBn<R>{{x, g, P, KK}, bn}; }
+};
 
+// The one way from a runtime tile id (0-4, see pick_tile) to launch<BM, BN>; fa / fb are
+// loader factories for the A (BM rows) and B (BN rows) operands.
+template <class EPI, class FA, class FB>
+static hipError_t launch_tiles(int tile, int M, int N, int K, int splits, hipStream_t st, const EPI& epi,
+                               const FA& fa, const FB& fb) {
+  if (tile == 1) return launch<256, 64>(fa.template make<256>(), fb.template make<64>(), epi, M, N, K, splits, st);
+  if (tile == 2) return launch<64, 256>(fa.template make<64>(), fb.template make<256>(), epi, M, N, K, splits, st);
+  if (tile == 3) return launch<256, 128>(fa.template make<256>(), fb.template make<128>(), epi, M, N, K, splits, st);
+  if (tile == 4) return launch<128, 256>(fa.template make<128>(), fb.template make<256>(), epi, M, N, K, splits, st);
+  return launch<128, 128>(fa.template make<128>(), fb.template make<128>(), epi, M, N, K, splits, st);
+}
 
+// ... and to the three-wide dense tiles (5: 128x96, 6: 128x192, 7: 128x288, see pick_dense_tile)
+template <class EPI, class FA, class FB>
+static hipError_t launch_dense_tiles(int dt, int M, int N, int K, int splits, hipStream_t st, const EPI& epi,
+                                     const FA& fa, const FB& fb) {
+  if (dt == 5) return launch<128, 96>(fa.template make<128>(), fb.template make<96>(), epi, M, N, K, splits, st);
+  if (dt == 6) return launch<128, 192>(fa.template make<128>(), fb.template make<192>(), epi, M, N, K, splits, st);
+  return launch<128, 288>(fa.template make<128>(), fb.template make<288>(), epi, M, N, K, splits, st);
+}
 
-// dispatch one GEMM over the three tile shapes; MK(R) builds the loaders for R rows
-#define MLC_TILE_DISPATCH(TILE, M, N, K, SPLITS, ST, EPI, MKA, MKB)                              \
-  do {                                                                                         \
-    if ((TILE) == 1) return launch<256, 64>(MKA(256), MKB(64), EPI, M, N, K, SPLITS, ST);      \
-    if ((TILE) == 2) return launch<64, 256>(MKA(64), MKB(256), EPI, M, N, K, SPLITS, ST);      \
-    if ((TILE) == 3) return launch<256, 128>(MKA(256), MKB(128), EPI, M, N, K, SPLITS, ST);    \
-    if ((TILE) == 4) return launch<128, 256>(MKA(128), MKB(256), EPI, M, N, K, SPLITS, ST);    \
-    return launch<128, 128>(MKA(128), MKB(128), EPI, M, N, K, SPLITS, ST);                     \
-  } while (0)
+// C = op(A) op(B) on the generic tiles for the four layouts of a plain-matrix GEMM:
+//   ta=0: A is [M][K] (lda);  ta=1: A is [K][M]
+//   tb=0: B is [K][N] (ldb);  tb=1: B is [N][K]
+template <class EPI>
+static hipError_t dispatch_ab(int ta, int tb, const bf16* A, int lda, const bf16* B, int ldb, int tile, int M, int N,
+                              int K, int splits, hipStream_t st, const EPI& epi) {
+  const MkMatKC a_kc{A, lda, M, K}, b_kc{B, ldb, N, K};
+  const MkMatMC a_mc{A, lda, K, M}, b_mc{B, ldb, K, N};
+  if (!ta && tb) return launch_tiles(tile, M, N, K, splits, st, epi, a_kc, b_kc);
+  if (!ta && !tb) return launch_tiles(tile, M, N, K, splits, st, epi, a_kc, b_mc);
+  if (ta && tb) return launch_tiles(tile, M, N, K, splits, st, epi, a_mc, b_kc);
+  return launch_tiles(tile, M, N, K, splits, st, epi, a_mc, b_mc);
+}
 
 MLC_EXPORT int mlc_bn_stat_copies() { return NSTAT; }
 
@@ -1756,27 +1841,16 @@ MLC_EXPORT int mlc_gemm_config(int prefetch) {
 // dense tile (-1 auto, 0 off, 5-7) / its split-K factor; returns the previous value
 // (-1: bad key)
 MLC_EXPORT int mlc_gemm_get_set(int key, int value) {
-  int* k = key == 0 ? &igemm::g_prefetch : key == 1 ? &igemm::g_split_target
-          : key == 2 ? &igemm::g_split_target_mat : key == 3 ? &igemm::g_big_tiles
-          : key == 4 ? &igemm::g_big_min_blocks : key == 5 ? &igemm::g_single_stage
-          : key == 6 ? &igemm::g_splitk_fused : key == 7 ? &igemm::g_dense_narrow
-          : key == 8 ? &igemm::g_gemm_dma : key == 9 ? &igemm::g_split_target_dense
-          : key == 10 ? &igemm::g_dense_tile : key == 11 ? &igemm::g_dense_split
-          : key == 12 ? &igemm::g_dense_bf16_split_target : key == 13 ? &igemm::g_single_stage_kt
-          : key == 14 ? &igemm::g_persist : key == 15 ? &igemm::g_persist_nbuf : key == 16 ? &igemm::g_persist_kt
-          : nullptr;
-  if (!k) return -1;
-  if (key == 14 && igemm::g_persist < 0) {   // resolve the env defaults (CU count) first
-    const char* e = getenv("MLC_GEMM_PERSIST");
-    igemm::g_persist = e ? atoi(e) : 0;
-    int dev = 0;
-    hipGetDevice(&dev);
-    hipDeviceGetAttribute(&igemm::g_num_cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (igemm::g_num_cus <= 0) igemm::g_num_cus = 256;
-  }
+  static int* const knobs[] = {
+      &g_prefetch, &g_split_target, &g_split_target_mat, &g_big_tiles, &g_big_min_blocks, &g_single_stage,
+      &g_splitk_fused, &g_dense_narrow, &g_gemm_dma, &g_split_target_dense, &g_dense_tile, &g_dense_split,
+      &g_dense_bf16_split_target, &g_single_stage_kt, &g_persist, &g_persist_nbuf, &g_persist_kt};
+  if (key < 0 || key >= (int)(sizeof(knobs) / sizeof(knobs[0]))) return -1;
+  int* k = knobs[key];
+  if (key == 14) resolve_persist_defaults();   // the env defaults (and the CU count) first
   if (key == 10 || key == 11) {   // resolve the env defaults before the first override
     int sp = 1;
-    (void)igemm::pick_dense_tile(4096, 768, 768, sp);
+    (void)pick_dense_tile(4096, 768, 768, sp);
   }
   const int old = *k;
   if (key == 10) {                // -1 = auto (pick_dense_tile's model), 0 = off, 5-7 = forced
@@ -1808,27 +1882,14 @@ static int conv_fwd_impl(const bf16* x, const bf16* w, bf16* y, int ldy, float* 
   epi.ncopy = g_mlc_ncopy;
   if (sum && g_mlc_det && (M + 63) / 64 > g_mlc_ncopy) return -2;   // one copy per 64-row group
   const BnIn bn{in_sc, in_sh};
-#define MKB(R) (MatKC<R>{w, K, Co, K})
+  const MkMatKC fb{w, K, Co, K};
   if (KH == 1 && KW == 1 && stride == 1 && pad == 0) {
-    if (in_sc) {
-#define MKA(R) (MatKCBn<R>{{x, C, M, K}, bn})
-      MLC_TILE_DISPATCH(tile, M, Co, K, 1, st, epi, MKA, MKB);
-#undef MKA
-    }
-#define MKA(R) (MatKC<R>{x, C, M, K})
-    MLC_TILE_DISPATCH(tile, M, Co, K, 1, st, epi, MKA, MKB);
-#undef MKA
+    if (in_sc) return launch_tiles(tile, M, Co, K, 1, st, epi, MkMatKCBn{x, C, M, K, bn}, fb);
+    return launch_tiles(tile, M, Co, K, 1, st, epi, MkMatKC{x, C, M, K}, fb);
   }
   const ConvGeom g = mkgeom(N, H, W, C, Co, KH, KW, stride, pad, dil, Ho, Wo);
-  if (in_sc) {
-#define MKA(R) (ConvFwdABn<R>{{x, g, M, K}, bn})
-    MLC_TILE_DISPATCH(tile, M, Co, K, 1, st, epi, MKA, MKB);
-#undef MKA
-  }
-#define MKA(R) (ConvFwdA<R>{x, g, M, K})
-  MLC_TILE_DISPATCH(tile, M, Co, K, 1, st, epi, MKA, MKB);
-#undef MKA
-#undef MKB
+  if (in_sc) return launch_tiles(tile, M, Co, K, 1, st, epi, MkConvFwdABn{x, g, M, K, bn}, fb);
+  return launch_tiles(tile, M, Co, K, 1, st, epi, MkConvFwdA{x, g, M, K}, fb);
 }
 
 MLC_EXPORT int mlc_conv_fwd(const bf16* x, const bf16* w, bf16* y, float* sum, float* sumsq,
@@ -1842,6 +1903,49 @@ MLC_EXPORT int mlc_conv_fwd_ld(const bf16* x, const bf16* w, bf16* y, int ldy, i
                                int KH, int KW, int stride, int pad, int dil, int Ho, int Wo, hipStream_t st) {
   return conv_fwd_impl(x, w, y, ldy, nullptr, nullptr, N, H, W, C, Co, KH, KW, stride, pad, dil, Ho, Wo, nullptr,
                        nullptr, st);
+}
+
+// Argument checks of the dgrad entries (0: fine); bn holds the fused BN-backward operands.
+static int dgrad_check(const BnBwdEpi& bn, int N, int H, int W, int C, int Co, int KH, int KW, int stride,
+                       const float* sum, const float* sumsq) {
+  if (C % 8 || Co % 8 || KH > 15 || KW > 16 || stride < 1 || ((sum == nullptr) != (sumsq == nullptr))) return -1;
+  if (bn.y0 && g_mlc_det && ((long)N * H * W + 63) / 64 > g_mlc_ncopy) return -2;
+  if (bn.msc0 && (!bn.msh0 || !bn.y0 || (bn.msc1 && (!bn.msh1 || !bn.y1)))) return -1;
+  if (bn.y0 && (!bn.mean0 || !bn.sums0 || (bn.y1 && (!bn.mean1 || !bn.sums1)))) return -1;
+  return 0;
+}
+
+// The general dgrad: one GEMM per stride-parity class of dx (see conv_dgrad_impl).  MkB is
+// the filter's loader factory: MkConvDgradB for w[Co][KH][KW][C], MkConvDgradBT for the
+// transposed, flipped wt[C][KH][KW][Co].  pad is the exports' (possibly packed) value.
+template <class MkB>
+static int dgrad_classes(const bf16* dy, const bf16* w, bf16* dx, const bf16* addend, const BnBwdEpi& bn,
+                         const ConvGeom& g, int pad, float* sum, float* sumsq, hipStream_t st) {
+  hipError_t err = hipSuccess;
+  // the parity-class GEMMs run one after another on the stream, so in deterministic mode
+  // the statistics stay reproducible as long as each launch has a copy per 64-row group
+  for (int ph = 0; ph < g.stride && ph < g.H; ++ph)
+    for (int pw = 0; pw < g.stride && pw < g.W; ++pw) {
+      const DgradClass cl = mkclass(g.stride, ph, pw, g.H, g.W, g.Ho, g.Wo, g.Co, g.KH, g.KW, pad, g.dil);
+      if (cl.nr > 15 || cl.ns > 16) return -1;
+      const int M = g.N * cl.Hc * cl.Wc, K = cl.nr * cl.ns * cl.ncb * BK;
+      if (M <= 0) continue;
+      if (sum && g_mlc_det && (M + 63) / 64 > g_mlc_ncopy) return -2;
+      const int tile = pick_tile(M, g.C);
+      const MkConvDgradA fa{dy, g, M, K, cl};
+      const MkB fb{w, g, cl};
+      if (g.stride == 1) {
+        EpiBF16<> epi{dx, g.C, sum, sumsq, IdentityRows{}, addend, bn};
+        epi.ncopy = g_mlc_ncopy;
+        err = launch_tiles(tile, M, g.C, K, 1, st, epi, fa, fb);
+      } else {
+        EpiBF16<ClassRows> epi{dx, g.C, sum, sumsq, ClassRows{cl, g.H, g.W}, addend, bn};
+        epi.ncopy = g_mlc_ncopy;
+        err = launch_tiles(tile, M, g.C, K, 1, st, epi, fa, fb);
+      }
+      if (err != hipSuccess) return err;
+    }
+  return err;
 }
 
 // dx[N,H,W,C] = conv_transpose(dy[N,Ho,Wo,Co], w) (+ addend, same layout as dx; may
@@ -1862,51 +1966,19 @@ static int conv_dgrad_impl(const bf16* dy, const bf16* w, bf16* dx, const bf16* 
                            const float* bn_mean1, float* bn_sums1, const float* bn_msc0,
                            const float* bn_msh0, const float* bn_msc1, const float* bn_msh1,
                            float* sum, float* sumsq, hipStream_t st) {
-  if (C % 8 || Co % 8 || KH > 15 || KW > 16 || stride < 1 || ((sum == nullptr) != (sumsq == nullptr))) return -1;
+  const BnBwdEpi bn{bn_mask, bn_y0, bn_mean0, bn_sums0, bn_y1, bn_mean1, bn_sums1,
+                    bn_msc0, bn_msh0, bn_msc1, bn_msh1, g_mlc_ncopy};
+  if (const int rc = dgrad_check(bn, N, H, W, C, Co, KH, KW, stride, sum, sumsq)) return rc;
   const ConvGeom g = mkgeom(N, H, W, C, Co, KH, KW, stride, pad, dil, Ho, Wo);
-  BnBwdEpi bn{bn_mask, bn_y0, bn_mean0, bn_sums0, bn_y1, bn_mean1, bn_sums1,
-              bn_msc0, bn_msh0, bn_msc1, bn_msh1, g_mlc_ncopy};
-  if (bn_y0 && g_mlc_det && ((long)N * H * W + 63) / 64 > g_mlc_ncopy) return -2;
-  if (bn_msc0 && (!bn_msh0 || !bn_y0 || (bn_msc1 && (!bn_msh1 || !bn_y1)))) return -1;
-  if (bn_y0 && (!bn_mean0 || !bn_sums0 || (bn_y1 && (!bn_mean1 || !bn_sums1)))) return -1;
   if (KH == 1 && KW == 1 && stride == 1 && pad == 0) {
     const DgradClass cl = mkclass(1, 0, 0, H, W, Ho, Wo, Co, 1, 1, 0, dil);
     const int M = N * H * W, K = cl.ncb * BK;
     if (sum && g_mlc_det && (M + 63) / 64 > g_mlc_ncopy) return -2;
-    const int tile = pick_tile(M, C);
     EpiBF16<> epi{dx, C, sum, sumsq, IdentityRows{}, addend, bn};
     epi.ncopy = g_mlc_ncopy;
-#define MKA(R) (MatKC<R>{dy, Co, M, Co})
-#define MKB(R) (ConvDgradB<R>{w, g, cl})
-    MLC_TILE_DISPATCH(tile, M, C, K, 1, st, epi, MKA, MKB);
-#undef MKA
+    return launch_tiles(pick_tile(M, C), M, C, K, 1, st, epi, MkMatKC{dy, Co, M, Co}, MkConvDgradB{w, g, cl});
   }
-  hipError_t err = hipSuccess;
-  // the parity-class GEMMs run one after another on the stream, so in deterministic mode
-  // the statistics stay reproducible as long as each launch has a copy per 64-row group
-  for (int ph = 0; ph < stride && ph < H; ++ph)
-    for (int pw = 0; pw < stride && pw < W; ++pw) {
-      const DgradClass cl = mkclass(stride, ph, pw, H, W, Ho, Wo, Co, KH, KW, pad, dil);
-      if (cl.nr > 15 || cl.ns > 16) return -1;
-      const int M = N * cl.Hc * cl.Wc, K = cl.nr * cl.ns * cl.ncb * BK;
-      if (M <= 0) continue;
-      if (sum && g_mlc_det && (M + 63) / 64 > g_mlc_ncopy) return -2;
-      const int tile = pick_tile(M, C);
-#define MKA(R) (ConvDgradA<R>{dy, g, M, K, cl})
-      if (stride == 1) {
-        EpiBF16<> epi{dx, C, sum, sumsq, IdentityRows{}, addend, bn};
-        epi.ncopy = g_mlc_ncopy;
-        err = [&]() -> hipError_t { MLC_TILE_DISPATCH(tile, M, C, K, 1, st, epi, MKA, MKB); }();
-      } else {
-        EpiBF16<ClassRows> epi{dx, C, sum, sumsq, ClassRows{cl, H, W}, addend, bn};
-        epi.ncopy = g_mlc_ncopy;
-        err = [&]() -> hipError_t { MLC_TILE_DISPATCH(tile, M, C, K, 1, st, epi, MKA, MKB); }();
-      }
-#undef MKA
-      if (err != hipSuccess) return err;
-    }
-  return err;
-#undef MKB
+  return dgrad_classes<MkConvDgradB>(dy, w, dx, addend, bn, g, pad, sum, sumsq, st);
 }
 
 MLC_EXPORT int mlc_conv_dgrad(const bf16* dy, const bf16* w, bf16* dx, const bf16* addend, int N,
@@ -1954,12 +2026,9 @@ MLC_EXPORT int mlc_conv_dgrad_t(const bf16* dy, const bf16* wt, bf16* dx, const 
                                 const float* bn_mean1, float* bn_sums1, const float* bn_msc0,
                                 const float* bn_msh0, const float* bn_msc1, const float* bn_msh1,
                                 hipStream_t st) {
-  if (C % 8 || Co % 8 || KH > 15 || KW > 16 || stride < 1) return -1;
-  if (bn_msc0 && (!bn_msh0 || !bn_y0 || (bn_msc1 && (!bn_msh1 || !bn_y1)))) return -1;
-  if (bn_y0 && (!bn_mean0 || !bn_sums0 || (bn_y1 && (!bn_mean1 || !bn_sums1)))) return -1;
-  BnBwdEpi bn{bn_mask, bn_y0, bn_mean0, bn_sums0, bn_y1, bn_mean1, bn_sums1,
-              bn_msc0, bn_msh0, bn_msc1, bn_msh1, g_mlc_ncopy};
-  if (bn_y0 && g_mlc_det && ((long)N * H * W + 63) / 64 > g_mlc_ncopy) return -2;
+  const BnBwdEpi bn{bn_mask, bn_y0, bn_mean0, bn_sums0, bn_y1, bn_mean1, bn_sums1,
+                    bn_msc0, bn_msh0, bn_msc1, bn_msh1, g_mlc_ncopy};
+  if (const int rc = dgrad_check(bn, N, H, W, C, Co, KH, KW, stride, nullptr, nullptr)) return rc;
   int pad_h, pad_w;
   unpack_pad(pad, pad_h, pad_w);
   const int ph = dil * (KH - 1) - pad_h, pw = dil * (KW - 1) - pad_w;
@@ -1968,46 +2037,16 @@ MLC_EXPORT int mlc_conv_dgrad_t(const bf16* dy, const bf16* wt, bf16* dx, const 
     const int M = N * H * W, K = KH * KW * Co;
     const int tile = pick_tile(M, C);
     EpiBF16<> epi{dx, C, nullptr, nullptr, IdentityRows{}, addend, bn};
-#define MKB(R) (MatKC<R>{wt, K, C, K})
-    if (KH == 1 && KW == 1) {
-#define MKA(R) (MatKC<R>{dy, Co, M, Co})
-      MLC_TILE_DISPATCH(tile, M, C, K, 1, st, epi, MKA, MKB);
-#undef MKA
-    }
+    const MkMatKC fb{wt, K, C, K};
+    if (KH == 1 && KW == 1) return launch_tiles(tile, M, C, K, 1, st, epi, MkMatKC{dy, Co, M, Co}, fb);
     // geometry of the equivalent forward conv: input dy [N, Ho, Wo, Co], output [N, H, W, C]
     const ConvGeom gf = mkgeom(N, Ho, Wo, Co, C, KH, KW, 1, pack_pad(ph, pw), dil, H, W);
-#define MKA(R) (ConvFwdA<R>{dy, gf, M, K})
-    MLC_TILE_DISPATCH(tile, M, C, K, 1, st, epi, MKA, MKB);
-#undef MKA
-#undef MKB
+    return launch_tiles(tile, M, C, K, 1, st, epi, MkConvFwdA{dy, gf, M, K}, fb);
   }
   const ConvGeom g = mkgeom(N, H, W, C, Co, KH, KW, stride, pad, dil, Ho, Wo);
-  hipError_t err = hipSuccess;
-  for (int qh = 0; qh < stride && qh < H; ++qh)
-    for (int qw = 0; qw < stride && qw < W; ++qw) {
-      const DgradClass cl = mkclass(stride, qh, qw, H, W, Ho, Wo, Co, KH, KW, pad, dil);
-      if (cl.nr > 15 || cl.ns > 16) return -1;
-      const int M = N * cl.Hc * cl.Wc, K = cl.nr * cl.ns * cl.ncb * BK;
-      if (M <= 0) continue;
-      const int tile = pick_tile(M, C);
-#define MKA(R) (ConvDgradA<R>{dy, g, M, K, cl})
-#define MKB(R) (ConvDgradBT<R>{wt, g, cl})
-      if (stride == 1) {
-        EpiBF16<> epi{dx, C, nullptr, nullptr, IdentityRows{}, addend, bn};
-        err = [&]() -> hipError_t { MLC_TILE_DISPATCH(tile, M, C, K, 1, st, epi, MKA, MKB); }();
-      } else {
-        EpiBF16<ClassRows> epi{dx, C, nullptr, nullptr, ClassRows{cl, H, W}, addend, bn};
-        err = [&]() -> hipError_t { MLC_TILE_DISPATCH(tile, M, C, K, 1, st, epi, MKA, MKB); }();
-      }
-#undef MKA
-#undef MKB
-      if (err != hipSuccess) return err;
-    }
-  return err;
+  return dgrad_classes<MkConvDgradBT>(dy, wt, dx, addend, bn, g, pad, nullptr, nullptr, st);
 }
 
-// dw[Co, KH*KW*C] (fp32) = sum_p dy[p][co] * im2col(x)[p][kk]; zeroes dw first unless
-// accumulate != 0.  splits <= 0 picks a split-K factor automatically.
 namespace {
 // out[i] (+)= sum over splits of ws[s][i]  (float4 per thread)
 __global__ void __launch_bounds__(256)
@@ -2032,6 +2071,38 @@ splitk_reduce_kernel(const float* __restrict__ ws, float* __restrict__ out, long
   }
 }
 }  // namespace
+
+// Split-K GEMM into the fp32 slabs ws[splits][slab] (plain stores, slab = M * N), then one
+// ordered pass that sums them into out (added to it when accumulate != 0).  splits is
+// already rounded (round_splits).
+template <class FA, class FB>
+static hipError_t launch_slabs_reduce(int tile, int M, int N, int K, int splits, hipStream_t st, float* ws,
+                                      size_t slab, float* out, int accumulate, const FA& fa, const FB& fb) {
+  const EpiF32Slab epi{ws, N, slab};
+  const hipError_t e = launch_tiles(tile, M, N, K, splits, st, epi, fa, fb);
+  if (e != hipSuccess) return e;
+  const long n4 = (long)slab / 4;
+  long blocks = (n4 + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, ws, out, n4, splits, n4, accumulate);
+  return hipGetLastError();
+}
+
+// The B operand of a conv weight gradient: x as the plain matrix [P][C] (a 1x1 stride-1
+// unpadded conv) or gathered (im2col), each with the BatchNorm + ReLU input transform when
+// bn is set (XF = false: entries without one, which keeps their kernels uninstantiated).
+// Calls f with the loader factory.
+template <bool XF, class F>
+static hipError_t with_wgrad_b(const bf16* x, const ConvGeom& g, int P, int KK, bool plain, const BnIn& bn, F f) {
+  if constexpr (XF) {
+    if (bn.sc) {
+      if (plain) return f(MkMatMCBn{x, g.C, P, g.C, bn});
+      return f(MkConvWgradBBn{x, g, P, KK, bn});
+    }
+  }
+  if (plain) return f(MkMatMC{x, g.C, P, g.C});
+  return f(MkConvWgradB{x, g, P, KK});
+}
 
 // dw[Co, KH*KW*C] (fp32) = sum_p dy[p][co] * im2col(x)[p][kk]; written, or added to dw
 // when accumulate != 0.  splits <= 0 picks a split-K factor automatically.  With a
@@ -2062,77 +2133,25 @@ MLC_EXPORT int mlc_conv_wgrad_native(const bf16* dy, const bf16* x, float* dw, i
     use_slab = ws && (long)(splits * slab) <= ws_floats;
   }
   const ConvGeom g = mkgeom(N, H, W, C, Co, KH, KW, stride, pad, dil, Ho, Wo);
-#define MKA(R) (MatMC<R>{dy, Co, P, Co})
+  const MkMatMC fa{dy, Co, P, Co};
   if (use_slab) {
-    {  // the launch rounds splits so that no split is empty: size the reduction to it
-      const int ktiles = (P + BK - 1) / BK;
-      const int per = (ktiles + splits - 1) / splits;
-      splits = (ktiles + per - 1) / per;
-    }
+    splits = round_splits((P + BK - 1) / BK, splits);   // size the reduction to what the launch runs
     const int BMv = tile_bm(tile), BNv = tile_bn(tile);
     if (unsigned* cnt = split_counters(st, (long)((Co + BMv - 1) / BMv) * ((KK + BNv - 1) / BNv), splits, BMv, BNv)) {
-      EpiSlabFused epi{ws, KK, slab, cnt, 0, dw, accumulate, {}};
-      if (in_sc) {
-#define MKB(R) (MatMCBn<R>{{x, C, P, C}, bn})
-        if (plain) MLC_TILE_DISPATCH(tile, Co, KK, P, splits, st, epi, MKA, MKB);
-#undef MKB
-#define MKB(R) (ConvWgradBBn<R>{{x, g, P, KK}, bn})
-        MLC_TILE_DISPATCH(tile, Co, KK, P, splits, st, epi, MKA, MKB);
-#undef MKB
-      }
-#define MKB(R) (MatMC<R>{x, C, P, C})
-      if (plain) MLC_TILE_DISPATCH(tile, Co, KK, P, splits, st, epi, MKA, MKB);
-#undef MKB
-#define MKB(R) (ConvWgradB<R>{x, g, P, KK})
-      MLC_TILE_DISPATCH(tile, Co, KK, P, splits, st, epi, MKA, MKB);
-#undef MKB
+      const EpiSlabFused epi{ws, KK, slab, cnt, 0, dw, accumulate, {}};
+      return with_wgrad_b<true>(x, g, P, KK, plain, bn, [&](const auto& fb) {
+        return launch_tiles(tile, Co, KK, P, splits, st, epi, fa, fb);
+      });
     }
-    EpiF32Slab epi{ws, KK, slab};
-    hipError_t e;
-    if (in_sc) {
-#define MKB(R) (MatMCBn<R>{{x, C, P, C}, bn})
-      if (plain) e = [&]() -> hipError_t { MLC_TILE_DISPATCH(tile, Co, KK, P, splits, st, epi, MKA, MKB); }();
-#undef MKB
-#define MKB(R) (ConvWgradBBn<R>{{x, g, P, KK}, bn})
-      else e = [&]() -> hipError_t { MLC_TILE_DISPATCH(tile, Co, KK, P, splits, st, epi, MKA, MKB); }();
-#undef MKB
-    } else {
-#define MKB(R) (MatMC<R>{x, C, P, C})
-      if (plain) e = [&]() -> hipError_t { MLC_TILE_DISPATCH(tile, Co, KK, P, splits, st, epi, MKA, MKB); }();
-#undef MKB
-#define MKB(R) (ConvWgradB<R>{x, g, P, KK})
-      else e = [&]() -> hipError_t { MLC_TILE_DISPATCH(tile, Co, KK, P, splits, st, epi, MKA, MKB); }();
-#undef MKB
-    }
-    if (e != hipSuccess) return e;
-    const long n4 = (long)slab / 4;
-    long blocks = (n4 + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, ws, dw, n4, splits,
-                       (long)slab / 4, accumulate);
-    return hipGetLastError();
+    return with_wgrad_b<true>(x, g, P, KK, plain, bn, [&](const auto& fb) {
+      return launch_slabs_reduce(tile, Co, KK, P, splits, st, ws, slab, dw, accumulate, fa, fb);
+    });
   }
   if (!accumulate) mlc_zero_f32(dw, (long)slab, st);
-  EpiF32Atomic epi{dw, KK};
-  if (in_sc) {
-    if (plain) {
-#define MKB(R) (MatMCBn<R>{{x, C, P, C}, bn})
-      MLC_TILE_DISPATCH(tile, Co, KK, P, splits, st, epi, MKA, MKB);
-#undef MKB
-    }
-#define MKB(R) (ConvWgradBBn<R>{{x, g, P, KK}, bn})
-    MLC_TILE_DISPATCH(tile, Co, KK, P, splits, st, epi, MKA, MKB);
-#undef MKB
-  }
-  if (plain) {
-#define MKB(R) (MatMC<R>{x, C, P, C})
-    MLC_TILE_DISPATCH(tile, Co, KK, P, splits, st, epi, MKA, MKB);
-#undef MKB
-  }
-#define MKB(R) (ConvWgradB<R>{x, g, P, KK})
-  MLC_TILE_DISPATCH(tile, Co, KK, P, splits, st, epi, MKA, MKB);
-#undef MKB
-#undef MKA
+  const EpiF32Atomic epi{dw, KK};
+  return with_wgrad_b<true>(x, g, P, KK, plain, bn, [&](const auto& fb) {
+    return launch_tiles(tile, Co, KK, P, splits, st, epi, fa, fb);
+  });
 }
 
 // Conv forward with a dense epilogue: y = act(conv(x, w) + bias) (act 0 / 3 = ReLU; the
@@ -2147,17 +2166,11 @@ MLC_EXPORT int mlc_conv_fwd_ex(const bf16* x, const bf16* w, bf16* y, const floa
   EpiBF16<IdentityRows, true> epi{y, Co, nullptr, nullptr, IdentityRows{}, nullptr};
   epi.bias = bias;
   epi.act = act;
-#define MKB(R) (MatKC<R>{w, K, Co, K})
-  if (KH == 1 && KW == 1 && stride == 1 && pad == 0) {
-#define MKA(R) (MatKC<R>{x, C, M, K})
-    MLC_TILE_DISPATCH(tile, M, Co, K, 1, st, epi, MKA, MKB);
-#undef MKA
-  }
+  const MkMatKC fb{w, K, Co, K};
+  if (KH == 1 && KW == 1 && stride == 1 && pad == 0)
+    return launch_tiles(tile, M, Co, K, 1, st, epi, MkMatKC{x, C, M, K}, fb);
   const ConvGeom g = mkgeom(N, H, W, C, Co, KH, KW, stride, pad, dil, Ho, Wo);
-#define MKA(R) (ConvFwdA<R>{x, g, M, K})
-  MLC_TILE_DISPATCH(tile, M, Co, K, 1, st, epi, MKA, MKB);
-#undef MKA
-#undef MKB
+  return launch_tiles(tile, M, Co, K, 1, st, epi, MkConvFwdA{x, g, M, K}, fb);
 }
 
 // Conv weight gradient plus the bias gradient: dw[Co][KH*KW*C] (+)= as mlc_conv_wgrad and
@@ -2174,49 +2187,23 @@ MLC_EXPORT int mlc_conv_wgrad_bias(const bf16* dy, const bf16* x, float* dw, flo
   const size_t slab = (size_t)Co * KK;
   int splits = g_mlc_det ? 1 : auto_splits(Co, KK, P, tile, plain ? g_split_target_mat : g_split_target);
   const ConvGeom g = mkgeom(N, H, W, C, Co, KH, KW, stride, pad, dil, Ho, Wo);
-#define MKA(R) (MatMCSum<R>{dy, Co, P, Co, dbias})
+  const MkMatMCSum fa{dy, Co, P, Co, dbias};
   if (ws && splits > 1 && (long)(splits * slab) <= ws_floats) {
-    const int ktiles = (P + BK - 1) / BK;
-    const int per = (ktiles + splits - 1) / splits;
-    splits = (ktiles + per - 1) / per;
-    EpiF32Slab epi{ws, KK, slab};
-    hipError_t e;
-#define MKB(R) (MatMC<R>{x, C, P, C})
-    if (plain) e = [&]() -> hipError_t { MLC_TILE_DISPATCH(tile, Co, KK, P, splits, st, epi, MKA, MKB); }();
-#undef MKB
-#define MKB(R) (ConvWgradB<R>{x, g, P, KK})
-    else e = [&]() -> hipError_t { MLC_TILE_DISPATCH(tile, Co, KK, P, splits, st, epi, MKA, MKB); }();
-#undef MKB
-    if (e != hipSuccess) return e;
-    const long n4 = (long)slab / 4;
-    long blocks = (n4 + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, ws, dw, n4, splits, n4, accumulate);
-    return hipGetLastError();
+    splits = round_splits((P + BK - 1) / BK, splits);
+    return with_wgrad_b<false>(x, g, P, KK, plain, BnIn{}, [&](const auto& fb) {
+      return launch_slabs_reduce(tile, Co, KK, P, splits, st, ws, slab, dw, accumulate, fa, fb);
+    });
   }
   if (!accumulate) mlc_zero_f32(dw, (long)slab, st);
-  EpiF32Atomic epi{dw, KK};
-  if (plain) {
-#define MKB(R) (MatMC<R>{x, C, P, C})
-    MLC_TILE_DISPATCH(tile, Co, KK, P, splits, st, epi, MKA, MKB);
-#undef MKB
-  }
-#define MKB(R) (ConvWgradB<R>{x, g, P, KK})
-  MLC_TILE_DISPATCH(tile, Co, KK, P, splits, st, epi, MKA, MKB);
-#undef MKB
-#undef MKA
+  const EpiF32Atomic epi{dw, KK};
+  return with_wgrad_b<false>(x, g, P, KK, plain, BnIn{}, [&](const auto& fb) {
+    return launch_tiles(tile, Co, KK, P, splits, st, epi, fa, fb);
+  });
 }
 
-// Generic bf16 GEMM with fp32 output: C[M][N] (+)= op(A) op(B) (+ bias)
-//   ta=0: A is [M][K] (lda);  ta=1: A is [K][M]
-//   tb=0: B is [K][N] (ldb);  tb=1: B is [N][K]
-// out_mode 0: store (+bias, accumulate flag), 1: atomic add (split-K allowed; the
-// caller zeroes C unless accumulating)
-#define GA_KC(R) (MatKC<R>{A, lda, M, K})
-#define GA_MC(R) (MatMC<R>{A, lda, K, M})
-#define GB_KC(R) (MatKC<R>{B, ldb, N, K})
-#define GB_MC(R) (MatMC<R>{B, ldb, K, N})
-
+// Generic bf16 GEMM with fp32 output: C[M][N] (+)= op(A) op(B) (+ bias), ta / tb as in
+// dispatch_ab.  out_mode 0: store (+bias, accumulate flag), 1: atomic add (split-K
+// allowed; the caller zeroes C unless accumulating)
 MLC_EXPORT int mlc_gemm_f32out(const bf16* A, const bf16* B, float* C, const float* bias,
                                int M, int N, int K, int lda, int ldb, int ldc, int ta, int tb,
                                int out_mode, int accumulate, int splits, hipStream_t st) {
@@ -2225,17 +2212,9 @@ MLC_EXPORT int mlc_gemm_f32out(const bf16* A, const bf16* B, float* C, const flo
   if (out_mode == 1) {
     if (splits <= 0) splits = auto_splits(M, N, K, tile, g_split_target_dense);
     if (g_mlc_det) splits = 1;
-    EpiF32Atomic epi{C, ldc};
-    if (!ta && tb) MLC_TILE_DISPATCH(tile, M, N, K, splits, st, epi, GA_KC, GB_KC);
-    if (!ta && !tb) MLC_TILE_DISPATCH(tile, M, N, K, splits, st, epi, GA_KC, GB_MC);
-    if (ta && tb) MLC_TILE_DISPATCH(tile, M, N, K, splits, st, epi, GA_MC, GB_KC);
-    MLC_TILE_DISPATCH(tile, M, N, K, splits, st, epi, GA_MC, GB_MC);
+    return dispatch_ab(ta, tb, A, lda, B, ldb, tile, M, N, K, splits, st, EpiF32Atomic{C, ldc});
   }
-  EpiF32 epi{C, ldc, bias, accumulate};
-  if (!ta && tb) MLC_TILE_DISPATCH(tile, M, N, K, 1, st, epi, GA_KC, GB_KC);
-  if (!ta && !tb) MLC_TILE_DISPATCH(tile, M, N, K, 1, st, epi, GA_KC, GB_MC);
-  if (ta && tb) MLC_TILE_DISPATCH(tile, M, N, K, 1, st, epi, GA_MC, GB_KC);
-  MLC_TILE_DISPATCH(tile, M, N, K, 1, st, epi, GA_MC, GB_MC);
+  return dispatch_ab(ta, tb, A, lda, B, ldb, tile, M, N, K, 1, st, EpiF32{C, ldc, bias, accumulate});
 }
 
 // Dense-layer weight + bias gradient in one GEMM: dW[M][N] += dY^T X (fp32 atomics,
@@ -2251,49 +2230,17 @@ MLC_EXPORT int mlc_linear_wgrad_bias_native(const bf16* A, const bf16* B, float*
   if (splits <= 0) splits = auto_splits(M, N, K, tile, g_split_target_dense);
   if (g_mlc_det) splits = 1;   // one dW atomic and one bias column-sum add per element
   const size_t slab = (size_t)M * N;
-#define GA_MCS(R) (MatMCSum<R>{A, lda, K, M, dbias})
+  const MkMatMCSum fa{A, lda, K, M, dbias};
+  const MkMatMC fb{B, ldb, K, N};
   if (ws && ldc == N && splits > 1 && (long)(splits * slab) <= ws_floats) {
-    const int ktiles = (K + BK - 1) / BK;
-    const int per = (ktiles + splits - 1) / splits;
-    splits = (ktiles + per - 1) / per;
+    splits = round_splits((K + BK - 1) / BK, splits);
     const int BMv = tile_bm(tile), BNv = tile_bn(tile);
-    if (unsigned* cnt = split_counters(st, (long)((M + BMv - 1) / BMv) * ((N + BNv - 1) / BNv), splits, BMv, BNv)) {
-      EpiSlabFused epi{ws, N, slab, cnt, 0, C, 1, {}};
-      MLC_TILE_DISPATCH(tile, M, N, K, splits, st, epi, GA_MCS, GB_MC);
-    }
-    EpiF32Slab epi{ws, N, slab};
-    const hipError_t e = [&]() -> hipError_t { MLC_TILE_DISPATCH(tile, M, N, K, splits, st, epi, GA_MCS, GB_MC); }();
-    if (e != hipSuccess) return e;
-    const long n4 = (long)slab / 4;
-    long blocks = (n4 + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, ws, C, n4, splits, n4, 1);
-    return hipGetLastError();
+    if (unsigned* cnt = split_counters(st, (long)((M + BMv - 1) / BMv) * ((N + BNv - 1) / BNv), splits, BMv, BNv))
+      return launch_tiles(tile, M, N, K, splits, st, EpiSlabFused{ws, N, slab, cnt, 0, C, 1, {}}, fa, fb);
+    return launch_slabs_reduce(tile, M, N, K, splits, st, ws, slab, C, 1, fa, fb);
   }
-  EpiF32Atomic epi{C, ldc};
-  MLC_TILE_DISPATCH(tile, M, N, K, splits, st, epi, GA_MCS, GB_MC);
-#undef GA_MCS
+  return launch_tiles(tile, M, N, K, splits, st, EpiF32Atomic{C, ldc}, fa, fb);
 }
-
-// bf16-output GEMM with a dense-layer epilogue: C = act(op(A) op(B) + bias) (pre-
-// activation to preact when given), or C = (op(A) op(B)) * act'(dact) (+ addend).
-
-// non-returning tile dispatch (for callers that continue after the GEMM)
-template <class EPI, class FA, class FB>
-static hipError_t launch_tiles(int tile, int M, int N, int K, int splits, hipStream_t st, const EPI& epi, FA fa,
-                               FB fb) {
-  if (tile == 1) return launch<256, 64>(fa.template make<256>(), fb.template make<64>(), epi, M, N, K, splits, st);
-  if (tile == 2) return launch<64, 256>(fa.template make<64>(), fb.template make<256>(), epi, M, N, K, splits, st);
-  if (tile == 3) return launch<256, 128>(fa.template make<256>(), fb.template make<128>(), epi, M, N, K, splits, st);
-  if (tile == 4) return launch<128, 256>(fa.template make<128>(), fb.template make<256>(), epi, M, N, K, splits, st);
-  return launch<128, 128>(fa.template make<128>(), fb.template make<128>(), epi, M, N, K, splits, st);
-}
-struct MkMatKC { const bf16* p; int ld, rows, K; template <int R> MatKC<R> make() const { return MatKC<R>{p, ld, rows, K}; } };
-struct MkMatMC { const bf16* p; int ld, K, cols; template <int R> MatMC<R> make() const { return MatMC<R>{p, ld, K, cols}; } };
-#define GA_KC_F (MkMatKC{A, lda, M, K})
-#define GA_MC_F (MkMatMC{A, lda, K, M})
-#define GB_KC_F (MkMatKC{B, ldb, N, K})
-#define GB_MC_F (MkMatMC{B, ldb, K, N})
 
 namespace {
 // Split-K finish for the dense GEMM: ws holds `splits` fp32 slabs [splits][M][N] of
@@ -2310,6 +2257,14 @@ dense_finalize_kernel(const float* __restrict__ ws, int splits, DenseFinish fin,
 }
 }  // namespace
 
+static hipError_t launch_dense_finalize(const float* ws, int splits, const DenseFinish& fin, int M, int N,
+                                        hipStream_t st) {
+  long blocks = ((long)M * (N / 8) + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(dense_finalize_kernel, dim3(blocks), dim3(256), 0, st, ws, splits, fin, M, N);
+  return hipGetLastError();
+}
+
 // bf16-output GEMM with a dense-layer epilogue: C = act(op(A) op(B) + bias) (pre-
 // activation to preact when given), or C = (op(A) op(B)) * act'(dact) (+ addend).
 // ws (optional, ws_floats fp32, any contents): when the output has too few tiles to fill
@@ -2323,29 +2278,23 @@ MLC_EXPORT int mlc_gemm_bf16_ex_native(const bf16* A, const bf16* B, bf16* C, in
   if (K % 8 || N % 8 || ldc % 8 || lda % 8 || ldb % 8 || (ta && M % 8)) return -1;
   const int ktiles = (K + BK - 1) / BK;
   const long slab = (long)M * N;
+  // the epilogue in the GEMM (unsplit), or in the pass that finishes split-K slabs
+  EpiBF16<IdentityRows, true> epi{C, ldc, nullptr, nullptr, IdentityRows{}, addend};
+  epi.bias = bias; epi.act = act; epi.preact = preact; epi.dact = dact;
+  const DenseFinish fin{C, ldc, bias, act, preact, addend, dact};
+  const MkMatKC a_kc{A, lda, M, K}, b_kc{B, ldb, N, K};
   if (!ta && tb) {  // both operands K-contiguous: the three-wide tiles apply
     int dsplit = 1;
     const int dt = pick_dense_tile(M, N, K, dsplit);
     if (dt >= 5 && dt <= 7) {
       if (dsplit > 1 && ws && slab * dsplit <= ws_floats && ktiles >= 2 * dsplit) {
-        const int per = (ktiles + dsplit - 1) / dsplit;
-        dsplit = (ktiles + per - 1) / per;
-        EpiF32Slab epi{ws, N, (size_t)slab};
-        hipError_t e = dt == 5 ? launch<128, 96>(GA_KC(128), GB_KC(96), epi, M, N, K, dsplit, st)
-                     : dt == 6 ? launch<128, 192>(GA_KC(128), GB_KC(192), epi, M, N, K, dsplit, st)
-                               : launch<128, 288>(GA_KC(128), GB_KC(288), epi, M, N, K, dsplit, st);
+        dsplit = round_splits(ktiles, dsplit);
+        const EpiF32Slab slabs{ws, N, (size_t)slab};
+        const hipError_t e = launch_dense_tiles(dt, M, N, K, dsplit, st, slabs, a_kc, b_kc);
         if (e != hipSuccess) return e;
-        const DenseFinish fin{C, ldc, bias, act, preact, addend, dact};
-        long blocks = ((long)M * (N / 8) + 255) / 256;
-        if (blocks > 8192) blocks = 8192;
-        hipLaunchKernelGGL(dense_finalize_kernel, dim3(blocks), dim3(256), 0, st, ws, dsplit, fin, M, N);
-        return hipGetLastError();
+        return launch_dense_finalize(ws, dsplit, fin, M, N, st);
       }
-      EpiBF16<IdentityRows, true> epi{C, ldc, nullptr, nullptr, IdentityRows{}, addend};
-      epi.bias = bias; epi.act = act; epi.preact = preact; epi.dact = dact;
-      if (dt == 5) return launch<128, 96>(GA_KC(128), GB_KC(96), epi, M, N, K, 1, st);
-      if (dt == 6) return launch<128, 192>(GA_KC(128), GB_KC(192), epi, M, N, K, 1, st);
-      return launch<128, 288>(GA_KC(128), GB_KC(288), epi, M, N, K, 1, st);
+      return launch_dense_tiles(dt, M, N, K, 1, st, epi, a_kc, b_kc);
     }
   }
   const int tile = pick_tile(M, N);
@@ -2360,45 +2309,22 @@ MLC_EXPORT int mlc_gemm_bf16_ex_native(const bf16* A, const bf16* B, bf16* C, in
     g_dense_narrow = e ? atoi(e) : 0;
   }
   if (g_dense_narrow && tile == 0 && N <= 1024 && tiles < 256 && ((M + 127) / 128) * ((N + 63) / 64) >= 256) {
-    EpiBF16<IdentityRows, true> epi{C, ldc, nullptr, nullptr, IdentityRows{}, addend};
-    epi.bias = bias; epi.act = act; epi.preact = preact; epi.dact = dact;
-    if (!ta && tb) return launch<128, 64>(GA_KC(128), GB_KC(64), epi, M, N, K, 1, st);
-    if (!ta && !tb) return launch<128, 64>(GA_KC(128), GB_MC(64), epi, M, N, K, 1, st);
+    if (!ta && tb) return launch<128, 64>(a_kc.make<128>(), b_kc.make<64>(), epi, M, N, K, 1, st);
+    if (!ta && !tb) return launch<128, 64>(a_kc.make<128>(), MkMatMC{B, ldb, K, N}.make<64>(), epi, M, N, K, 1, st);
   }
   if (ws)
     while (tiles * splits < g_dense_bf16_split_target && ktiles / (splits * 2) >= 4 && slab * splits * 2 <= ws_floats)
       splits *= 2;
   if (splits > 1) {
-    {  // the launch rounds splits so that no split is empty: finish exactly those slabs
-      const int per = (ktiles + splits - 1) / splits;
-      splits = (ktiles + per - 1) / per;
-    }
-    const DenseFinish fin{C, ldc, bias, act, preact, addend, dact};
-    if (unsigned* cnt = split_counters(st, tiles, splits, BMv, BNv)) {
-      EpiSlabFused epi{ws, N, (size_t)slab, cnt, 1, nullptr, 0, fin};
-      if (!ta && tb) return launch_tiles(tile, M, N, K, splits, st, epi, GA_KC_F, GB_KC_F);
-      if (!ta && !tb) return launch_tiles(tile, M, N, K, splits, st, epi, GA_KC_F, GB_MC_F);
-      if (ta && tb) return launch_tiles(tile, M, N, K, splits, st, epi, GA_MC_F, GB_KC_F);
-      return launch_tiles(tile, M, N, K, splits, st, epi, GA_MC_F, GB_MC_F);
-    }
-    EpiF32Slab epi{ws, N, (size_t)slab};
-    hipError_t e;
-    if (!ta && tb) e = launch_tiles(tile, M, N, K, splits, st, epi, GA_KC_F, GB_KC_F);
-    else if (!ta && !tb) e = launch_tiles(tile, M, N, K, splits, st, epi, GA_KC_F, GB_MC_F);
-    else if (ta && tb) e = launch_tiles(tile, M, N, K, splits, st, epi, GA_MC_F, GB_KC_F);
-    else e = launch_tiles(tile, M, N, K, splits, st, epi, GA_MC_F, GB_MC_F);
+    splits = round_splits(ktiles, splits);   // finish exactly the slabs the launch writes
+    if (unsigned* cnt = split_counters(st, tiles, splits, BMv, BNv))
+      return dispatch_ab(ta, tb, A, lda, B, ldb, tile, M, N, K, splits, st,
+                         EpiSlabFused{ws, N, (size_t)slab, cnt, 1, nullptr, 0, fin});
+    const hipError_t e = dispatch_ab(ta, tb, A, lda, B, ldb, tile, M, N, K, splits, st, EpiF32Slab{ws, N, (size_t)slab});
     if (e != hipSuccess) return e;
-    long blocks = ((long)M * (N / 8) + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(dense_finalize_kernel, dim3(blocks), dim3(256), 0, st, ws, splits, fin, M, N);
-    return hipGetLastError();
+    return launch_dense_finalize(ws, splits, fin, M, N, st);
   }
-  EpiBF16<IdentityRows, true> epi{C, ldc, nullptr, nullptr, IdentityRows{}, addend};
-  epi.bias = bias; epi.act = act; epi.preact = preact; epi.dact = dact;
-  if (!ta && tb) MLC_TILE_DISPATCH(tile, M, N, K, 1, st, epi, GA_KC, GB_KC);
-  if (!ta && !tb) MLC_TILE_DISPATCH(tile, M, N, K, 1, st, epi, GA_KC, GB_MC);
-  if (ta && tb) MLC_TILE_DISPATCH(tile, M, N, K, 1, st, epi, GA_MC, GB_KC);
-  MLC_TILE_DISPATCH(tile, M, N, K, 1, st, epi, GA_MC, GB_MC);
+  return dispatch_ab(ta, tb, A, lda, B, ldb, tile, M, N, K, 1, st, epi);
 }
 
 // bf16-output GEMM (same layout flags)
@@ -2406,9 +2332,5 @@ MLC_EXPORT int mlc_gemm_bf16out(const bf16* A, const bf16* B, bf16* C, int M, in
                                 int lda, int ldb, int ldc, int ta, int tb, hipStream_t st) {
   if (K % 8 || N % 8 || ldc % 8 || lda % 8 || ldb % 8 || (ta && M % 8)) return -1;
   const int tile = pick_tile(M, N);
-  EpiBF16<> epi{C, ldc, nullptr, nullptr, IdentityRows{}};
-  if (!ta && tb) MLC_TILE_DISPATCH(tile, M, N, K, 1, st, epi, GA_KC, GB_KC);
-  if (!ta && !tb) MLC_TILE_DISPATCH(tile, M, N, K, 1, st, epi, GA_KC, GB_MC);
-  if (ta && tb) MLC_TILE_DISPATCH(tile, M, N, K, 1, st, epi, GA_MC, GB_KC);
-  MLC_TILE_DISPATCH(tile, M, N, K, 1, st, epi, GA_MC, GB_MC);
+  return dispatch_ab(ta, tb, A, lda, B, ldb, tile, M, N, K, 1, st, EpiBF16<>{C, ldc, nullptr, nullptr, IdentityRows{}});
 }
