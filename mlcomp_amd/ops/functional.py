@@ -585,6 +585,46 @@ def bn_bwd(dz, z, y, mean, invstd, gamma, want_dres=False, dgamma=None, dbeta=No
     return dy, dres
 
 
+# BN-backward apply + dgrad + wgrad of a narrow-in / wide-out 1x1 ConvBN unit in one kernel
+# (csrc/kernels/conv1x1_bwd.hip): dy is formed on the fly and never written.
+# MLC_FUSE_1X1_BWD=0 keeps the three-kernel path (bn_bwd -> conv2d_dgrad -> conv2d_wgrad).
+FUSE_1X1_BWD = os.environ.get('MLC_FUSE_1X1_BWD', '1') == '1'
+
+
+def conv1x1_bn_bwd_available(Cin, Cout) -> bool:
+    """True when the fused kernel has an instantiation for (Cin, Cout) and the mode allows it
+    (not deterministic mode: the per-block weight-gradient atomics are unordered)."""
+    return not _lib.DETERMINISTIC and bool(_lib.load().mlc_conv1x1_bn_bwd_ok(Cin, Cout))
+
+
+def conv1x1_bn_bwd(dz, y, x, w, mean, invstd, gamma, sums, dgamma, dbeta, dw,
+                   addend: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                   bn: Optional[BnBwdSpec] = None) -> torch.Tensor:
+    """Backward of z = BN(conv1x1(x, w)) given the complete BN-backward partial sums
+    (``sums``, as :func:`bn_bwd` with ``prereduced=True``): writes dgamma / dbeta, ADDS the
+    weight gradient to ``dw`` (fp32 [Co, 1, 1, Ci]) and returns dx (+ ``addend``; ``out`` may
+    alias it).  ``bn``: the single-y affine (ReLU) :class:`BnBwdSpec` of the previous BN, as
+    in :func:`conv2d_dgrad`.  On the CPU it is the three reference ops in sequence."""
+    Co, KH, KW, Ci = w.shape
+    assert (KH, KW) == (1, 1) and y.shape[-1] == Co and x.shape[-1] == Ci, (w.shape, y.shape, x.shape)
+    assert bn is None or (bn.mask is None and len(bn.ys) == 1 and bn.affine is not None)
+    if _cuda(dz):
+        rows = y.numel() // Co
+        dx = out if out is not None else torch.empty_like(x)
+        p = [None] * 5
+        if bn is not None:
+            (yk, mk, sk), (ak, hk) = bn.ys[0], bn.affine[0]
+            p = [yk, mk, sk, ak, hk]
+        _lib.call('mlc_conv1x1_bn_bwd', _lib.ptr(dz), _lib.ptr(y), _lib.ptr(x), _lib.ptr(w), _lib.ptr(mean),
+                  _lib.ptr(invstd), _lib.ptr(gamma), _lib.ptr(sums), _lib.ptr(dgamma), _lib.ptr(dbeta),
+                  _lib.ptr(dw), _lib.ptr(dx), _lib.ptr(addend), *[_lib.ptr(t) for t in p], rows, Ci, Co,
+                  _lib.stream())
+        return dx
+    dy, _ = bn_bwd(dz, None, y, mean, invstd, gamma, dgamma=dgamma, dbeta=dbeta, sums=sums, prereduced=True)
+    conv2d_wgrad(dy, x, w.shape, out=dw, accumulate=True)
+    return conv2d_dgrad(dy, w, x.shape, addend=addend, out=out, bn=bn)
+
+
 # ---------------------------------------------------------------- pooling
 def pool_out_hw(H, W, k, s, p, ceil_mode=False):
     """nn.MaxPool2d's output size (ceil_mode: the last window may start in the right / bottom

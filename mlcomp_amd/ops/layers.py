@@ -336,6 +336,20 @@ class ConvBN:
         if self.s2d:
             self.w.grad.mul_(self._gmask)
 
+    def _fused_1x1_bwd_ok(self, dz, x, dgrad_bn) -> bool:
+        """The unit's backward can run as the one fused kernel (MLC_FUSE_1X1_BWD, default on):
+        a plain 1x1 / stride-1 / pad-0 conv on the GPU whose (Cin, Cout) has an instantiation,
+        outside deterministic mode, with no BN reduction in the dgrad epilogue or the
+        single-y affine (ReLU) one."""
+        if not (Fn.FUSE_1X1_BWD and dz.is_cuda and type(self) is ConvBN and not self.s2d):
+            return False
+        if self.k != (1, 1) or self.stride != 1 or self.pad != 0 or x.shape[-1] != self.cin_p:
+            return False
+        if dgrad_bn is not None and (dgrad_bn.mask is not None or len(dgrad_bn.ys) != 1
+                                     or dgrad_bn.affine is None):
+            return False
+        return Fn.conv1x1_bn_bwd_available(self.cin_p, self.Co)
+
     def bwd(self, dz, rec, want_dres=False, dx_addend=None, need_dx=True, dx_out=None,
             prereduced=False, dgrad_bn=None, in_affine=None, defer: Optional[list] = None):
         """``defer`` (with a wgrad stream): leave the weight gradient running on the side
@@ -343,6 +357,18 @@ class ConvBN:
         the stream later and then marks the slot ready."""
         x, y, z = rec
         arena = self.ctx.arena
+        if need_dx and prereduced and in_affine is None and self._fused_1x1_bwd_ok(dz, x, dgrad_bn):
+            # one kernel: BN-backward apply + dgrad + wgrad (Fn.conv1x1_bn_bwd); dy is never
+            # written, so there is no side-stream weight gradient to fork, defer or join
+            if not self.ctx.grad_prezeroed:
+                self.w.grad.zero_()
+            dx = Fn.conv1x1_bn_bwd(dz, y, x, self.w.bf16, self.save_mean, self.save_invstd,
+                                   self.gamma.master, self.ctx.ws[self.k_bw], self.gamma.grad,
+                                   self.beta.grad, self.w.grad, addend=dx_addend, out=dx_out, bn=dgrad_bn)
+            arena.mark_ready(self.gamma)
+            arena.mark_ready(self.beta)
+            arena.mark_ready(self.w)
+            return dx, (dz if want_dres else None)
         dy, dres = Fn.bn_bwd(dz, z if self.act else None, y, self.save_mean, self.save_invstd,
                              self.gamma.master, want_dres=want_dres, dgamma=self.gamma.grad,
                              dbeta=self.beta.grad, sums=self.ctx.ws[self.k_bw], zero_sums=False,
