@@ -93,6 +93,9 @@ _SIGS = {
     'mlc_conv1x1_bn_bwd': [vp] * 18 + [i64, i32, i32, vp],
     'mlc_conv1x1_bn_bwd_ok': [i32, i32],
     'mlc_conv1x1_bwd_get_set': [i32, i32],
+    'mlc_conv1x1_fwd': [vp] * 5 + [i64, i32, i32, vp],
+    'mlc_conv1x1_fwd_ok': [i32, i32],
+    'mlc_conv1x1_fwd_get_set': [i32, i32],
     'mlc_maxpool_fwd': [vp, vp, vp] + [i32] * 9 + [vp],
     'mlc_maxpool_bwd': [vp, vp, vp] + [i32] * 9 + [vp],
     'mlc_stem_pool_fwd': [vp] * 6 + [i32] * 4 + [vp],
@@ -196,6 +199,8 @@ def load():
                 lib.mlc_bn_get_set(key, int(os.environ[env]))
         if os.environ.get('MLC_FUSE_1X1_BLOCKS'):   # block cap of the fused 1x1 backward (0: one per CU)
             lib.mlc_conv1x1_bwd_get_set(0, int(os.environ['MLC_FUSE_1X1_BLOCKS']))
+        if os.environ.get('MLC_CONV1X1_FWD_BLOCKS'):   # block cap of the streaming 1x1 forward (0: one per CU)
+            lib.mlc_conv1x1_fwd_get_set(0, int(os.environ['MLC_CONV1X1_FWD_BLOCKS']))
         if DETERMINISTIC:
             lib.mlc_set_deterministic(1, DET_COPIES)
             # torch's own scatter-adds (the BERT embedding gradients) take their

@@ -90,6 +90,34 @@ def conv2d_fwd(x: torch.Tensor, w: torch.Tensor, stride=1, pad=0, dil=1,
     return y
 
 
+# Channel-expanding 1x1 / stride-1 / pad-0 forward with BN statistics as a weight-stationary
+# streaming kernel (csrc/kernels/conv1x1_fwd.hip): y is bit-identical to the igemm path.
+# MLC_CONV1X1_FWD=0 keeps the igemm path (conv2d_fwd).
+CONV1X1_FWD = os.environ.get('MLC_CONV1X1_FWD', '1') == '1'
+
+
+def conv1x1_fwd_available(Cin, Cout) -> bool:
+    """True when the streaming kernel has an instantiation for (Cin, Cout) and the mode allows
+    it (not deterministic mode: the per-block statistics atomics are unordered)."""
+    return not _lib.DETERMINISTIC and bool(_lib.load().mlc_conv1x1_fwd_ok(Cin, Cout))
+
+
+def conv1x1_fwd(x: torch.Tensor, w: torch.Tensor, stats: Tuple[torch.Tensor, torch.Tensor],
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = conv1x1(x, w) in NHWC with the BN partial sums of y and y^2 accumulated into
+    ``stats``, exactly as :func:`conv2d_fwd` with stride 1, pad 0 and ``stats``; GPU tensors
+    run the streaming kernel (a shape without an instantiation raises)."""
+    Co, KH, KW, Ci = w.shape
+    assert (KH, KW) == (1, 1) and x.shape[-1] == Ci and stats is not None, (w.shape, x.shape)
+    if not _cuda(x):
+        return conv2d_fwd(x, w, stats=stats, out=out)
+    y = out if out is not None else torch.empty(*x.shape[:-1], Co, device=x.device, dtype=torch.bfloat16)
+    assert y.is_contiguous() and x.is_contiguous(), (y.stride(), x.stride())
+    _lib.call('mlc_conv1x1_fwd', _lib.ptr(x), _lib.ptr(w), _lib.ptr(y), _lib.ptr(stats[0]), _lib.ptr(stats[1]),
+              x.numel() // Ci, Ci, Co, _lib.stream())
+    return y
+
+
 def conv_transpose2d_fwd(x: torch.Tensor, w: torch.Tensor, out_hw, stride=2, pad=1, dil=1,
                          stats: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
     """y = conv_transpose(x, w) in NHWC, no bias: x [N, Hi, Wi, Cin], w [Cin, KH, KW, Cout]

@@ -303,7 +303,19 @@ class ConvBN:
     def _conv(self, x, stats, in_affine=None):
         if self.s2d and in_affine is None:
             return Fn.stem_conv_fwd(x, self.w.bf16, stats=stats)
+        if stats is not None and in_affine is None and self._conv1x1_fwd_ok(x):
+            return Fn.conv1x1_fwd(x, self.w.bf16, stats)
         return Fn.conv2d_fwd(x, self.w.bf16, self.stride, self.pad, self.dil, stats=stats, in_affine=in_affine)
+
+    def _conv1x1_fwd_ok(self, x) -> bool:
+        """The training forward can run as the streaming kernel (MLC_CONV1X1_FWD, default on): a
+        plain 1x1 / stride-1 / pad-0 conv on the GPU whose (Cin, Cout) has an instantiation,
+        outside deterministic mode."""
+        if not (Fn.CONV1X1_FWD and x.is_cuda and type(self) is ConvBN and not self.s2d):
+            return False
+        if self.k != (1, 1) or self.stride != 1 or self.pad != 0 or x.shape[-1] != self.cin_p:
+            return False
+        return Fn.conv1x1_fwd_available(self.cin_p, self.Co)
 
     def _dgrad(self, dy, x_shape, addend=None, out=None, bn=None):
         wt = None
