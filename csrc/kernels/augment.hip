@@ -30,12 +30,12 @@ __device__ __forceinline__ Box box(const int* par, int b, int oh, int ow) {
   return r;
 }
 
-// bilinear sample of the box at output pixel (oy, ox): out[c] for c < C
+// bilinear sample of the box at row u / column v of its resize (scales sy, sx = box /
+// grid): out[c] for c < C.  Half-pixel centres, clamped at the box edge.
 template <int C>
-__device__ __forceinline__ void sample(const uint8_t* img, int W, const Box& bx, int oy, int ox, int ow,
-                                       float* out) {
-  if (bx.flip) ox = ow - 1 - ox;
-  float fy = ((float)oy + 0.5f) * bx.sy - 0.5f, fx = ((float)ox + 0.5f) * bx.sx - 0.5f;
+__device__ __forceinline__ void sample_at(const uint8_t* img, int W, const Box& bx, int u, int v, float sy,
+                                          float sx, float* out) {
+  float fy = ((float)u + 0.5f) * sy - 0.5f, fx = ((float)v + 0.5f) * sx - 0.5f;
   fy = fminf(fmaxf(fy, 0.f), (float)(bx.h - 1));
   fx = fminf(fmaxf(fx, 0.f), (float)(bx.w - 1));
   const int y0 = (int)fy, x0 = (int)fx;
@@ -52,6 +52,14 @@ __device__ __forceinline__ void sample(const uint8_t* img, int W, const Box& bx,
     const float bot = (float)p10[c] + wx * ((float)p11[c] - (float)p10[c]);
     out[c] = top + wy * (bot - top);
   }
+}
+
+// the classification transform at output pixel (oy, ox): horizontal flip, then the sample
+template <int C>
+__device__ __forceinline__ void sample(const uint8_t* img, int W, const Box& bx, int oy, int ox, int ow,
+                                       float* out) {
+  if (bx.flip) ox = ow - 1 - ox;
+  sample_at<C>(img, W, bx, oy, ox, bx.sy, bx.sx, out);
 }
 
 template <int C>
@@ -115,6 +123,138 @@ augment_pix_kernel(const uint8_t* __restrict__ src, const int* __restrict__ par,
   }
 }
 
+// ---- segmentation: image + mask under one geometric transform (mlc_augment_seg) ----
+// par: per sample {y0, x0, h, w, hflip, vflip, transpose, 0}.  Output pixel (oy, ox) reads
+// the box at row u of gh and column v of gw:
+//   transpose ? (u, v, gh, gw) = (ox, oy, ow, oh) : (oy, ox, oh, ow);
+//   hflip: v = gw-1-v;  vflip: u = gh-1-u.
+// The image is sample_at(u, v) with scales h/gh, w/gw; the mask is the nearest source
+// pixel in integers, row ((2u+1)*h) / (2*gh), column ((2v+1)*w) / (2*gw), which lies in
+// the box without clamping.
+struct SegBox {
+  Box bx;   // origin, size and the scales h/gh, w/gw (flip unused)
+  int y0, x0, gh, gw, hflip, vflip, tr;
+};
+
+// The box is clamped into the image, so no par can make a thread read outside
+// [0,H) x [0,W); a box the host loader draws is unchanged by it.
+__device__ __forceinline__ SegBox seg_box(const int* par, int b, int H, int W, int oh, int ow) {
+  const int* p = par + 8 * b;
+  SegBox s;
+  s.y0 = min(max(p[0], 0), H - 1);
+  s.x0 = min(max(p[1], 0), W - 1);
+  s.bx.h = min(max(p[2], 1), H - s.y0);
+  s.bx.w = min(max(p[3], 1), W - s.x0);
+  s.hflip = p[4]; s.vflip = p[5]; s.tr = p[6];
+  s.gh = s.tr ? ow : oh;
+  s.gw = s.tr ? oh : ow;
+  s.bx.y0 = (float)s.y0; s.bx.x0 = (float)s.x0; s.bx.flip = 0;
+  s.bx.sy = (float)s.bx.h / (float)s.gh;
+  s.bx.sx = (float)s.bx.w / (float)s.gw;
+  return s;
+}
+
+__device__ __forceinline__ void seg_coord(const SegBox& s, int oy, int ox, int& u, int& v) {
+  u = s.tr ? ox : oy;
+  v = s.tr ? oy : ox;
+  if (s.hflip) v = s.gw - 1 - v;
+  if (s.vflip) u = s.gh - 1 - u;
+}
+
+// mask of output pixel `pix` (= (b*oh + oy)*ow + ox) from grid position (u, v): planes
+// (kind 0) fp32 0/1 [pix][K], index (kind 1) int64 [pix]
+__device__ __forceinline__ void write_mask(const uint8_t* mask, int W, int K, int kind, const SegBox& s, int u,
+                                           int v, void* out, long pix) {
+  const int row = ((2 * u + 1) * s.bx.h) / (2 * s.gh), col = ((2 * v + 1) * s.bx.w) / (2 * s.gw);
+  const uint8_t* m = mask + ((size_t)(s.y0 + row) * W + s.x0 + col) * K;
+  if (kind == 1) {
+    reinterpret_cast<long long*>(out)[pix] = (long long)m[0];
+  } else if (K == 4) {
+    const uint32_t w = *reinterpret_cast<const uint32_t*>(m);
+    float4 f;
+    f.x = (w & 0xffu) ? 1.f : 0.f;
+    f.y = (w & 0xff00u) ? 1.f : 0.f;
+    f.z = (w & 0xff0000u) ? 1.f : 0.f;
+    f.w = (w & 0xff000000u) ? 1.f : 0.f;
+    reinterpret_cast<float4*>(out)[pix] = f;
+  } else {
+    float* o = reinterpret_cast<float*>(out) + pix * K;
+    for (int k = 0; k < K; ++k) o[k] = m[k] ? 1.f : 0.f;
+  }
+}
+
+__global__ void __launch_bounds__(NT)
+augment_seg_s2d_kernel(const uint8_t* __restrict__ src, const uint8_t* __restrict__ msk,
+                       const int* __restrict__ par, const float* __restrict__ ms, bf16* __restrict__ out,
+                       void* __restrict__ out_mask, int B, int H, int W, int K, int kind, int oh, int ow, int Hb,
+                       int Wb) {
+  constexpr int C = 3;
+  const long total = (long)B * Hb * Wb;
+  for (long q = (long)blockIdx.x * NT + threadIdx.x; q < total; q += (long)gridDim.x * NT) {
+    const int j = (int)(q % Wb);
+    const long t = q / Wb;
+    const int i = (int)(t % Hb);
+    const int b = (int)(t / Hb);
+    const SegBox s = seg_box(par, b, H, W, oh, ow);
+    const uint8_t* img = src + (size_t)b * H * W * C;
+    const uint8_t* mask = msk + (size_t)b * H * W * K;
+    float v[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) v[e] = 0.f;
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 2; ++dx) {
+        const int oy = 2 * i + dy - 3, ox = 2 * j + dx - 3;   // stem padding 3
+        if ((unsigned)oy < (unsigned)oh && (unsigned)ox < (unsigned)ow) {
+          int gu, gv;
+          seg_coord(s, oy, ox, gu, gv);
+          float f[C];
+          sample_at<C>(img, W, s.bx, gu, gv, s.bx.sy, s.bx.sx, f);
+#pragma unroll
+          for (int c = 0; c < C; ++c) v[(dy * 2 + dx) * 3 + c] = (f[c] - ms[c]) * ms[4 + c];
+          write_mask(mask, W, K, kind, s, gu, gv, out_mask, ((long)b * oh + oy) * ow + ox);
+        }
+      }
+    uint4* dst = reinterpret_cast<uint4*>(out + q * 16);
+    dst[0] = pack8(v);
+    dst[1] = pack8(v + 8);
+  }
+}
+
+template <int C>
+__global__ void __launch_bounds__(NT)
+augment_seg_pix_kernel(const uint8_t* __restrict__ src, const uint8_t* __restrict__ msk,
+                       const int* __restrict__ par, const float* __restrict__ ms, void* __restrict__ out,
+                       void* __restrict__ out_mask, int B, int H, int W, int K, int kind, int oh, int ow,
+                       int layout) {
+  const long total = (long)B * oh * ow;
+  for (long q = (long)blockIdx.x * NT + threadIdx.x; q < total; q += (long)gridDim.x * NT) {
+    const int ox = (int)(q % ow);
+    const long t = q / ow;
+    const int oy = (int)(t % oh);
+    const int b = (int)(t / oh);
+    const SegBox s = seg_box(par, b, H, W, oh, ow);
+    int gu, gv;
+    seg_coord(s, oy, ox, gu, gv);
+    float f[C];
+    sample_at<C>(src + (size_t)b * H * W * C, W, s.bx, gu, gv, s.bx.sy, s.bx.sx, f);
+    if (layout == 1) {
+      float v[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = 0.f;
+#pragma unroll
+      for (int c = 0; c < C; ++c) v[c] = (f[c] - ms[c]) * ms[4 + c];
+      *reinterpret_cast<uint4*>(reinterpret_cast<bf16*>(out) + q * 8) = pack8(v);
+    } else {
+      float* o = reinterpret_cast<float*>(out);
+#pragma unroll
+      for (int c = 0; c < C; ++c) o[(((size_t)b * C + c) * oh + oy) * ow + ox] = (f[c] - ms[c]) * ms[4 + c];
+    }
+    write_mask(msk + (size_t)b * H * W * K, W, K, kind, s, gu, gv, out_mask, q);
+  }
+}
+
 }  // namespace
 
 // mean_istd: 8 floats {mean[0..3], 1/std[0..3]} (uint8 scale) on the device
@@ -139,5 +279,40 @@ MLC_EXPORT int mlc_augment(const uint8_t* src, const int* par, const float* mean
   else if (C == 3) AUG_PIX(3);
   else AUG_PIX(4);
 #undef AUG_PIX
+  return hipGetLastError();
+}
+
+// Image + mask records under one transform: img [B][H][W][C], mask [B][H][W][K] uint8,
+// par int32 [B][8] = {y0, x0, h, w, hflip, vflip, transpose, 0}.  out_img: `layout` as
+// in mlc_augment; out_mask: mask_kind 0 (planes) fp32 0/1 [B][oh][ow][K] in pixel order,
+// mask_kind 1 (index, K = 1) int64 [B][oh][ow].  One launch; a thread derives the source
+// coordinate of its output pixel once and samples both operands there.  Returns -1 for
+// arguments out of range; par lives on the device, so its boxes are clamped into the
+// image by the kernel instead.
+MLC_EXPORT int mlc_augment_seg(const uint8_t* img, const uint8_t* mask, const int* par, const float* mean_istd,
+                               void* out_img, void* out_mask, int B, int H, int W, int C, int K, int oh, int ow,
+                               int layout, int mask_kind, hipStream_t st) {
+  if (C < 1 || C > 4 || K < 1 || K > 4 || B <= 0 || H <= 0 || W <= 0 || oh <= 0 || ow <= 0 || layout < 0 ||
+      layout > 2 || mask_kind < 0 || mask_kind > 1)
+    return -1;
+  if (mask_kind == 1 && K != 1) return -1;
+  if (layout == 0 && (C != 3 || (oh & 1) || (ow & 1))) return -1;
+  if (!img || !mask || !par || !mean_istd || !out_img || !out_mask) return -1;
+  const int Hb = (oh + 6) / 2, Wb = (ow + 6) / 2;
+  const long total = layout == 0 ? (long)B * Hb * Wb : (long)B * oh * ow;
+  long blocks = (total + NT - 1) / NT;
+  if (blocks > 16384) blocks = 16384;
+  if (layout == 0) {
+    hipLaunchKernelGGL(augment_seg_s2d_kernel, dim3((int)blocks), dim3(NT), 0, st, img, mask, par, mean_istd,
+                       reinterpret_cast<bf16*>(out_img), out_mask, B, H, W, K, mask_kind, oh, ow, Hb, Wb);
+    return hipGetLastError();
+  }
+#define AUG_SEG(CC) hipLaunchKernelGGL(augment_seg_pix_kernel<CC>, dim3((int)blocks), dim3(NT), 0, st, img, mask, \
+                                       par, mean_istd, out_img, out_mask, B, H, W, K, mask_kind, oh, ow, layout)
+  if (C == 1) AUG_SEG(1);
+  else if (C == 2) AUG_SEG(2);
+  else if (C == 3) AUG_SEG(3);
+  else AUG_SEG(4);
+#undef AUG_SEG
   return hipGetLastError();
 }

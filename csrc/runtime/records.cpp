@@ -17,6 +17,16 @@
 //   u64 record_bytes (= H*W*C + 4); u8 reserved[24]
 // followed by `count` records {u8 image[H][W][C]; i32 label}.
 //
+// Segmentation files carry a mask instead of a label: magic "MLSEG001", label_bytes =
+// H*W*K, record_bytes = H*W*(C+K), reserved[0..3] = u32 K (mask planes, 1..4),
+// reserved[4..7] = u32 kind (0: planes, a pixel is foreground for plane k iff its byte is
+// non-zero; 1: index, K = 1 and the byte is the class id); records
+// {u8 image[H][W][C]; u8 mask[H][W][K]}.  The other magic keeps either reader from
+// opening the other kind of file.  The segmentation loader (mlr_seg_*) is the same slot
+// state machine with a mask buffer in place of the labels and params[batch][8] =
+// {y0, x0, h, w, hflip, vflip, transpose, 0}: the box draws are the classification ones,
+// then three independent coins that span the eight symmetries of the square.
+//
 // Slot protocol: the caller registers `depth` slots (image buffer of batch*H*W*C bytes,
 // int64 labels[batch], int32 params[batch][5]); next() blocks until the next batch of the
 // epoch (in order) is complete and returns its slot, release(slot) hands it back.  Batches
@@ -41,6 +51,7 @@
 namespace {
 
 constexpr char MAGIC[8] = {'M', 'L', 'R', 'E', 'C', '0', '0', '1'};
+constexpr char SEG_MAGIC[8] = {'M', 'L', 'S', 'E', 'G', '0', '0', '1'};
 
 struct Header {
   char magic[8];
@@ -55,6 +66,7 @@ struct RecordFile {
   const uint8_t* map = nullptr;
   size_t size = 0;
   Header h{};
+  uint32_t K = 0, kind = 0;   // mask planes and kind of a segmentation file (K = 0: labels)
   const uint8_t* record(uint64_t i) const { return map + sizeof(Header) + i * h.record_bytes; }
 };
 
@@ -77,7 +89,8 @@ enum SlotState { FREE = 0, FILLING = 1, READY = 2, INUSE = 3 };
 
 struct Slot {
   uint8_t* img = nullptr;
-  int64_t* lab = nullptr;
+  int64_t* lab = nullptr;    // classification
+  uint8_t* mask = nullptr;   // segmentation
   int32_t* par = nullptr;
   SlotState state = FREE;
   int64_t batch = -1;
@@ -91,6 +104,7 @@ struct Loader {
   uint64_t seed;
   int rank, world, shuffle, drop_last;
   int chunk = 16;
+  bool seg = false;   // image + mask records, params[batch][8]
   std::vector<Slot> slots;
   // epoch
   uint64_t epoch = 0;
@@ -104,15 +118,25 @@ struct Loader {
 
   int chunks_per_batch() const { return (batch + chunk - 1) / chunk; }
 
-  // one sample's augmentation: {y0, x0, h, w, flip} of the source box
+  int par_stride() const { return seg ? 8 : 5; }
+
+  // one sample's augmentation: the source box {y0, x0, h, w}, then {flip} or, for
+  // segmentation, {hflip, vflip, transpose, 0}
   void params(uint64_t sample, int32_t* p) const {
     const int H = (int)rf->h.H, W = (int)rf->h.W;
     Rng g(seed * 0x100000001b3ull ^ (epoch << 40) ^ sample);
+    for (int i = 4; i < par_stride(); ++i) p[i] = 0;
     if (!train) {   // centre crop of the output size (whole image if it is smaller)
       const int h = std::min(H, out_h), w = std::min(W, out_w);
-      p[0] = (H - h) / 2; p[1] = (W - w) / 2; p[2] = h; p[3] = w; p[4] = 0;
+      p[0] = (H - h) / 2; p[1] = (W - w) / 2; p[2] = h; p[3] = w;
       return;
     }
+    draw_box(g, H, W, p);
+    const int coins = seg ? 3 : 1;
+    for (int i = 0; i < coins; ++i) p[4 + i] = (int)(g.next() & 1);
+  }
+
+  void draw_box(Rng& g, int H, int W, int32_t* p) const {
     const double area = (double)H * W;
     for (int attempt = 0; attempt < 10; ++attempt) {   // torchvision RandomResizedCrop
       const double a = area * (smin + (smax - smin) * g.uniform());
@@ -122,25 +146,30 @@ struct Loader {
       if (w > 0 && h > 0 && w <= W && h <= H) {
         p[0] = (int)(g.next() % (uint64_t)(H - h + 1));
         p[1] = (int)(g.next() % (uint64_t)(W - w + 1));
-        p[2] = h; p[3] = w; p[4] = (int)(g.next() & 1);
+        p[2] = h; p[3] = w;
         return;
       }
     }
     const int s = std::min(H, W);   // fallback: centre square
-    p[0] = (H - s) / 2; p[1] = (W - s) / 2; p[2] = s; p[3] = s; p[4] = (int)(g.next() & 1);
+    p[0] = (H - s) / 2; p[1] = (W - s) / 2; p[2] = s; p[3] = s;
   }
 
   void fill(Slot& sl, int64_t b, int c) {
     const size_t ib = (size_t)rf->h.H * rf->h.W * rf->h.C;
+    const size_t mb = (size_t)rf->h.H * rf->h.W * rf->K;
     const int i0 = c * chunk, i1 = std::min(batch, i0 + chunk);
     for (int i = i0; i < i1; ++i) {
       const uint64_t s = order[(size_t)b * batch + i];
       const uint8_t* rec = rf->record(s);
       std::memcpy(sl.img + (size_t)i * ib, rec, ib);
-      int32_t lab;
-      std::memcpy(&lab, rec + ib, 4);
-      sl.lab[i] = lab;
-      params(s, sl.par + 5 * i);
+      if (seg) {
+        std::memcpy(sl.mask + (size_t)i * mb, rec + ib, mb);
+      } else {
+        int32_t lab;
+        std::memcpy(&lab, rec + ib, 4);
+        sl.lab[i] = lab;
+      }
+      params(s, sl.par + par_stride() * i);
     }
   }
 
@@ -238,7 +267,9 @@ struct Loader {
 
 #define MLR_EXPORT extern "C" __attribute__((visibility("default")))
 
-MLR_EXPORT void* mlr_open(const char* path) {
+namespace {
+
+RecordFile* open_file(const char* path, bool seg) {
   auto* rf = new RecordFile();
   rf->fd = open(path, O_RDONLY);
   struct stat st{};
@@ -253,8 +284,19 @@ MLR_EXPORT void* mlr_open(const char* path) {
   rf->map = (const uint8_t*)m;
   std::memcpy(&rf->h, rf->map, sizeof(Header));
   const uint64_t need = sizeof(Header) + rf->h.count * rf->h.record_bytes;
-  if (std::memcmp(rf->h.magic, MAGIC, 8) != 0 || rf->h.label_bytes != 4 ||
-      rf->h.record_bytes != (uint64_t)rf->h.H * rf->h.W * rf->h.C + 4 || need > rf->size || rf->h.count == 0) {
+  const uint64_t ib = (uint64_t)rf->h.H * rf->h.W * rf->h.C;
+  bool ok;
+  if (seg) {
+    std::memcpy(&rf->K, rf->h.reserved, 4);
+    std::memcpy(&rf->kind, rf->h.reserved + 4, 4);
+    const uint64_t mb = (uint64_t)rf->h.H * rf->h.W * rf->K;
+    ok = std::memcmp(rf->h.magic, SEG_MAGIC, 8) == 0 && rf->K >= 1 && rf->K <= 4 && rf->kind <= 1 &&
+         (rf->kind == 0 || rf->K == 1) && rf->h.C >= 1 && rf->h.C <= 4 && rf->h.label_bytes == mb &&
+         rf->h.record_bytes == ib + mb;
+  } else {
+    ok = std::memcmp(rf->h.magic, MAGIC, 8) == 0 && rf->h.label_bytes == 4 && rf->h.record_bytes == ib + 4;
+  }
+  if (!ok || need > rf->size || rf->h.count == 0) {
     munmap(m, rf->size);
     close(rf->fd);
     delete rf;
@@ -262,6 +304,47 @@ MLR_EXPORT void* mlr_open(const char* path) {
   }
   madvise(m, rf->size, MADV_RANDOM);
   return rf;
+}
+
+Loader* create_loader(void* file, bool seg, int batch, int out_h, int out_w, int train, double smin, double smax,
+                      double rmin, double rmax, uint64_t seed, int rank, int world, int shuffle, int drop_last,
+                      int threads, int chunk) {
+  if (!file || batch <= 0 || world <= 0 || rank < 0 || rank >= world || threads <= 0) return nullptr;
+  if ((((const RecordFile*)file)->K != 0) != seg) return nullptr;   // the other kind of file
+  auto* L = new Loader();
+  L->rf = (const RecordFile*)file;
+  L->seg = seg;
+  L->batch = batch; L->out_h = out_h; L->out_w = out_w; L->train = train;
+  L->smin = smin; L->smax = smax; L->rmin = rmin; L->rmax = rmax;
+  L->seed = seed; L->rank = rank; L->world = world; L->shuffle = shuffle; L->drop_last = drop_last;
+  L->chunk = chunk > 0 ? chunk : 16;
+  for (int i = 0; i < threads; ++i) L->workers.emplace_back([L] { L->worker(); });
+  return L;
+}
+
+int set_slot(Loader* L, int i, uint8_t* img, int64_t* lab, uint8_t* mask, int32_t* par) {
+  std::lock_guard<std::mutex> lk(L->mu);
+  if (L->started || i < 0) return -1;
+  if ((int)L->slots.size() <= i) L->slots.resize((size_t)i + 1);
+  L->slots[(size_t)i].img = img;
+  L->slots[(size_t)i].lab = lab;
+  L->slots[(size_t)i].mask = mask;
+  L->slots[(size_t)i].par = par;
+  return 0;
+}
+
+}  // namespace
+
+MLR_EXPORT void* mlr_open(const char* path) { return open_file(path, false); }
+
+// an image + mask file; closed with mlr_close
+MLR_EXPORT void* mlr_seg_open(const char* path) { return open_file(path, true); }
+
+// shape[0..5] = count, H, W, C, K, kind
+MLR_EXPORT void mlr_seg_shape(void* h, uint64_t* shape) {
+  const auto* rf = (const RecordFile*)h;
+  shape[0] = rf->h.count; shape[1] = rf->h.H; shape[2] = rf->h.W; shape[3] = rf->h.C;
+  shape[4] = rf->K; shape[5] = rf->kind;
 }
 
 // shape[0..3] = count, H, W, C
@@ -282,27 +365,29 @@ MLR_EXPORT void mlr_close(void* h) {
 MLR_EXPORT void* mlr_loader_create(void* file, int batch, int out_h, int out_w, int train, double smin, double smax,
                                    double rmin, double rmax, uint64_t seed, int rank, int world, int shuffle,
                                    int drop_last, int threads, int chunk) {
-  if (!file || batch <= 0 || world <= 0 || rank < 0 || rank >= world || threads <= 0) return nullptr;
-  auto* L = new Loader();
-  L->rf = (const RecordFile*)file;
-  L->batch = batch; L->out_h = out_h; L->out_w = out_w; L->train = train;
-  L->smin = smin; L->smax = smax; L->rmin = rmin; L->rmax = rmax;
-  L->seed = seed; L->rank = rank; L->world = world; L->shuffle = shuffle; L->drop_last = drop_last;
-  L->chunk = chunk > 0 ? chunk : 16;
-  for (int i = 0; i < threads; ++i) L->workers.emplace_back([L] { L->worker(); });
-  return L;
+  return create_loader(file, false, batch, out_h, out_w, train, smin, smax, rmin, rmax, seed, rank, world, shuffle,
+                       drop_last, threads, chunk);
 }
 
 // register ring slot `i` (call for every slot before the first epoch)
 MLR_EXPORT int mlr_loader_set_slot(void* h, int i, uint8_t* img, int64_t* lab, int32_t* par) {
+  return set_slot((Loader*)h, i, img, lab, nullptr, par);
+}
+
+// the loader of an mlr_seg_open file: train != 0 draws the box as above plus hflip, vflip and
+// transpose coins; start_epoch / next / release / destroy are the mlr_loader_* ones
+MLR_EXPORT void* mlr_seg_loader_create(void* file, int batch, int out_h, int out_w, int train, double smin,
+                                       double smax, double rmin, double rmax, uint64_t seed, int rank, int world,
+                                       int shuffle, int drop_last, int threads, int chunk) {
+  return create_loader(file, true, batch, out_h, out_w, train, smin, smax, rmin, rmax, seed, rank, world, shuffle,
+                       drop_last, threads, chunk);
+}
+
+// slot `i`: image batch*H*W*C bytes, mask batch*H*W*K bytes, int32 par[batch][8]
+MLR_EXPORT int mlr_seg_loader_set_slot(void* h, int i, uint8_t* img, uint8_t* mask, int32_t* par) {
   auto* L = (Loader*)h;
-  std::lock_guard<std::mutex> lk(L->mu);
-  if (L->started || i < 0) return -1;
-  if ((int)L->slots.size() <= i) L->slots.resize((size_t)i + 1);
-  L->slots[(size_t)i].img = img;
-  L->slots[(size_t)i].lab = lab;
-  L->slots[(size_t)i].par = par;
-  return 0;
+  if (!L->seg) return -1;
+  return set_slot(L, i, img, nullptr, mask, par);
 }
 
 // (re)start at `epoch`; returns the number of batches this rank yields in it
@@ -312,7 +397,7 @@ MLR_EXPORT int64_t mlr_loader_start_epoch(void* h, uint64_t epoch) {
     std::lock_guard<std::mutex> lk(L->mu);
     if (L->slots.empty()) return -1;
     for (auto& s : L->slots)
-      if (!s.img || !s.lab || !s.par) return -1;
+      if (!s.img || !(L->seg ? (void*)s.mask : (void*)s.lab) || !s.par) return -1;
   }
   L->start_epoch(epoch);
   return L->nbatches;

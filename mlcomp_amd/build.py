@@ -11,8 +11,9 @@
   launched at `mlcomp/server/__main__.py:66-79`).
 * ``libmlcomp_runtime.so`` - host-side C++ runtime (``csrc/runtime``): the memory-mapped
   record files and the threaded batch gatherer of the native input pipeline
-  (:mod:`mlcomp_amd.train.records`); ``mlcomp-records-selftest-<san>`` is its
-  ThreadSanitizer / AddressSanitizer self-test.
+  (:mod:`mlcomp_amd.train.records`); ``mlcomp-records-selftest-<san>`` and
+  ``mlcomp-records-seg-selftest-<san>`` are its ThreadSanitizer / AddressSanitizer
+  self-tests.
 
 Outputs live under ``mlcomp_amd/_native/`` so they travel with the repo snapshot.
 Compilation is incremental (mtime based) and parallel.
@@ -141,13 +142,16 @@ def build_runtime(verbose=False):
     return RUNTIME_LIB
 
 
-def build_runtime_selftest(sanitize='tsan', verbose=False):
-    """The record loader's self-test driver linked with an instrumented copy of the
-    runtime sources (``tsan``: ThreadSanitizer, ``asan``: AddressSanitizer + UBSan)."""
+def build_runtime_selftest(sanitize='tsan', verbose=False, main='records_selftest.cpp'):
+    """A record loader self-test driver (``main``, a file of ``csrc/runtime``:
+    ``records_selftest.cpp`` or ``records_seg_selftest.cpp``) linked with an instrumented
+    copy of the runtime sources (``tsan``: ThreadSanitizer, ``asan``: AddressSanitizer +
+    UBSan)."""
     os.makedirs(OUT, exist_ok=True)
-    main = os.path.join(ROOT, 'csrc', 'runtime', 'records_selftest.cpp')
+    name = os.path.splitext(os.path.basename(main))[0].replace('_', '-')   # records-selftest, ...
+    main = os.path.join(ROOT, 'csrc', 'runtime', os.path.basename(main))
     srcs = _runtime_srcs() + [main]
-    out = os.path.join(OUT, f'mlcomp-records-selftest-{sanitize}')
+    out = os.path.join(OUT, f'mlcomp-{name}-{sanitize}')
     if _newer(out, srcs + glob.glob(os.path.join(ROOT, 'csrc', 'runtime', '*.h'))):
         cxx = shutil.which('g++') or 'c++'
         _link_atomic([cxx, '-O1', '-g', '-std=c++17', '-pthread', '-Wall'] + SANITIZERS[sanitize] + ['-o'], out, srcs)

@@ -99,5 +99,40 @@ def pack_records(img_path, out, size, fold_csv, fold, exclude_fold):
     click.echo(f'{n} images, {len(names)} classes -> {out}')
 
 
+@main.command('pack-seg-records')
+@click.argument('img_path')
+@click.argument('mask_path')
+@click.argument('out')
+@click.option('--size', type=int, default=256, help='stored square size (shorter side resized, centre crop)')
+@click.option('--kind', type=click.Choice(['planes', 'index']), default='planes',
+              help='planes: non-zero mask bytes are foreground; index: the byte is the class id')
+@click.option('--fold-csv', default=None, help='fold.csv (image,mask,fold): pack the rows of --fold only')
+@click.option('--fold', type=int, default=None)
+@click.option('--exclude-fold', is_flag=True, help='pack every fold except --fold (the training split)')
+def pack_seg_records(img_path, mask_path, out, size, kind, fold_csv, fold, exclude_fold):
+    """Pack an image folder and a mask folder (files paired by name, as split-segment pairs
+    them) or the rows of a fold.csv into an image + mask .mlrec record file."""
+    from mlcomp_amd.train.records import pack_seg_images
+    if fold_csv:
+        import pandas as pd
+        df = pd.read_csv(fold_csv)
+        if fold is not None:
+            df = df[(df['fold'] != fold) if exclude_fold else (df['fold'] == fold)]
+        images, masks = list(df['image']), list(df['mask'])
+    else:
+        by_stem = lambda n: os.path.splitext(n)[0]  # noqa: E731
+        images, masks = sorted(os.listdir(img_path), key=by_stem), sorted(os.listdir(mask_path), key=by_stem)
+    stem = lambda names: [os.path.splitext(n)[0] for n in names]  # noqa: E731
+    if stem(images) != stem(masks):
+        odd = sorted(set(stem(images)) ^ set(stem(masks)))
+        raise click.ClickException(f'{img_path} and {mask_path} do not pair up by name'
+                                   + (f': {", ".join(odd[:5])}' if odd else ' (order or duplicates)'))
+    if not images:
+        raise click.ClickException('no image / mask pairs')
+    n = pack_seg_images([join(img_path, p) for p in images], [join(mask_path, p) for p in masks], out,
+                        size=size, kind=kind)
+    click.echo(f'{n} image / mask pairs ({kind}) -> {out}')
+
+
 if __name__ == '__main__':
     main()

@@ -98,9 +98,19 @@ class NativeSegmentationStep(GraphedStep):
             return Fn.stem_s2d(x_nhwc, 3)
         return x_nhwc
 
-    def load_batch(self, images: torch.Tensor, masks: torch.Tensor):
+    def load_batch(self, images: torch.Tensor, masks: torch.Tensor, pixel_order: bool = False):
         """Copy a batch into the static buffers: images NCHW float (or NHWC bf16 padded),
-        masks [N, K, H, W] / [N, H, W] in {0, 1}."""
+        masks [N, K, H, W] / [N, H, W] in {0, 1}.  ``pixel_order``: the batch is already what
+        the buffers hold (``SegRecordLoader`` with ``mask_order='pixel'``): images in the
+        stem's layout and fp32 masks [N, H, W, K], one ``copy_`` each."""
+        if pixel_order:
+            images = self._prep(images)     # a no-op for the stem's own layout
+            if images.shape != self.x.shape or images.dtype != self.x.dtype or masks.numel() != self.t.numel():
+                raise ValueError(f'pixel-order batch {tuple(images.shape)} {images.dtype} / {tuple(masks.shape)} '
+                                 f'does not fit the step ({tuple(self.x.shape)}, {self.t.numel()} mask values)')
+            self.x.copy_(images, non_blocking=True)
+            self.t.copy_(masks.reshape(-1), non_blocking=True)
+            return
         x = images
         if x.dim() == 4 and x.shape[1] in (1, 3) and x.dtype != torch.bfloat16:
             x = Fn.nchw_to_nhwc(x.to(self.device, non_blocking=True).float(), pad_to=STEM_CIN)

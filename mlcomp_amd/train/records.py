@@ -16,10 +16,17 @@ split between the host and the GPU instead.
   ``csrc/kernels/augment.hip``) crops, resizes, flips, normalises and writes the layout
   the model reads (the native ResNet stem's space-to-depth image, NHWC8 or NCHW fp32).
 * :func:`augment_reference` is the same transform in PyTorch (CPU path, test oracle).
+* Segmentation: ``MLSEG001`` files pair every image with a uint8 mask
+  (:func:`write_seg_records`, :func:`pack_seg_images`, :class:`SegRecordFile`).
+  :class:`SegRecordLoader` runs the same ring over them; the host draws the crop box plus
+  hflip / vflip / transpose coins (the eight symmetries of the square) and one kernel
+  (``mlc_augment_seg``) samples the image bilinearly and the mask by nearest neighbour at
+  the same source coordinate.  :func:`augment_seg_reference` is its PyTorch twin.
 """
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 import math
 import weakref
 import os
@@ -31,6 +38,9 @@ import torch
 
 MAGIC = b'MLREC001'
 HEADER = struct.Struct('<8s4I2Q24x')
+SEG_MAGIC = b'MLSEG001'
+SEG_HEADER = struct.Struct('<8s4I2Q2I16x')   # ... count, record_bytes, K, kind
+MASK_KINDS = {'planes': 0, 'index': 1}
 LAYOUTS = {'s2d': 0, 'nhwc8': 1, 'nchw': 2}
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -116,6 +126,111 @@ class RecordFile:
         return int(np.asarray(self._m[i, -4:]).view('<i4')[0])
 
 
+def write_seg_records(path: str, images: Iterable, masks: Iterable, kind: str = 'planes') -> int:
+    """Write uint8 HWC ``images`` and their uint8 ``masks`` ([H, W, K] or [H, W]) to an
+    image + mask record file; returns the record count.  ``kind='planes'``: K = 1..4 binary
+    planes, a pixel is foreground for plane k iff its byte is non-zero; ``kind='index'``:
+    K = 1, the byte is the class id.  Written to ``path + '.tmp'`` and renamed."""
+    if kind not in MASK_KINDS:
+        raise ValueError(f'mask kind: planes / index, not {kind!r}')
+    it, mit = iter(images), iter(masks)
+    tmp = path + '.tmp'
+    n = 0
+    H = W = Cc = K = None
+
+    def header(count):
+        return SEG_HEADER.pack(SEG_MAGIC, H, W, Cc, H * W * K, count, H * W * (Cc + K), K, MASK_KINDS[kind])
+    try:
+        with open(tmp, 'wb') as f:
+            for img, m in zip(it, mit):
+                a = np.ascontiguousarray(img, dtype=np.uint8)
+                m = np.ascontiguousarray(m, dtype=np.uint8)
+                if m.ndim == 2:
+                    m = m[:, :, None]
+                if H is None:
+                    (H, W, Cc), K = a.shape, m.shape[2]
+                if n == 0:
+                    if not (1 <= Cc <= 4 and 1 <= K <= 4) or (kind == 'index' and K != 1):
+                        raise ValueError(f'{Cc} image channels / {K} {kind} mask planes: 1..4 each, index masks 1')
+                    f.write(header(0))
+                if a.shape != (H, W, Cc) or m.shape != (H, W, K):
+                    raise ValueError(f'record {n}: shapes {a.shape} / {m.shape} != {(H, W, Cc)} / {(H, W, K)}')
+                f.write(a.tobytes())
+                f.write(m.tobytes())
+                n += 1
+            if n == 0:
+                raise ValueError('no records')
+            f.seek(0)
+            f.write(header(n))
+    except BaseException:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        raise
+    os.replace(tmp, path)
+    return n
+
+
+def pack_seg_images(image_paths: Sequence[str], mask_paths: Sequence[str], out: str, size: int = 256,
+                    kind: str = 'planes') -> int:
+    """Decode image / mask file pairs (PIL) into an image + mask record file: the image's
+    shorter side is resized to ``size`` (bilinear) and a ``size`` x ``size`` square is
+    centre-cropped; the mask gets the same geometry with nearest resampling.  Masks are
+    read as one 8-bit plane ('L'; palette files keep their indices)."""
+    from PIL import Image
+    if len(image_paths) != len(mask_paths):
+        raise ValueError(f'{len(image_paths)} images but {len(mask_paths)} masks')
+
+    def fit(im, resample):
+        w, h = im.size
+        s = size / min(w, h)
+        im = im.resize((max(size, round(w * s)), max(size, round(h * s))), resample)
+        w, h = im.size
+        l, t = (w - size) // 2, (h - size) // 2
+        return np.asarray(im.crop((l, t, l + size, t + size)), dtype=np.uint8)
+
+    def pairs():
+        for ip, mp in zip(image_paths, mask_paths):
+            im, m = Image.open(ip).convert('RGB'), Image.open(mp)
+            if m.mode not in ('L', 'P'):
+                m = m.convert('L')
+            if im.size != m.size:
+                raise ValueError(f'{ip}: image {im.size} and mask {m.size} differ in size')
+            yield fit(im, Image.BILINEAR), fit(m, Image.NEAREST)
+    # zip() in the writer draws from the two branches in turn, so tee holds one pair at most
+    a, b = itertools.tee(pairs())
+    return write_seg_records(out, (p[0] for p in a), (p[1] for p in b), kind=kind)
+
+
+class SegRecordFile:
+    """numpy view of an image + mask record file (the python twin of ``mlr_seg_open``)."""
+
+    def __init__(self, path: str):
+        with open(path, 'rb') as f:
+            raw = f.read(SEG_HEADER.size)
+        if len(raw) < SEG_HEADER.size:
+            raise ValueError(f'{path}: not an image + mask mlrec file')
+        magic, H, W, Cc, lb, n, rb, K, kind = SEG_HEADER.unpack(raw)
+        if magic != SEG_MAGIC or not 1 <= K <= 4 or kind > 1 or (kind == 1 and K != 1) or not 1 <= Cc <= 4 \
+                or lb != H * W * K or rb != H * W * (Cc + K):
+            raise ValueError(f'{path}: not an image + mask mlrec file')
+        self.shape = (H, W, Cc)
+        self.planes = K
+        self.kind = 'index' if kind else 'planes'
+        self.count = n
+        self._m = np.memmap(path, dtype=np.uint8, mode='r', offset=SEG_HEADER.size, shape=(n, rb))
+
+    def __len__(self):
+        return self.count
+
+    def image(self, i: int) -> np.ndarray:
+        H, W, Cc = self.shape
+        return np.asarray(self._m[i, :H * W * Cc]).reshape(H, W, Cc)
+
+    def mask(self, i: int) -> np.ndarray:
+        H, W, Cc = self.shape
+        return np.asarray(self._m[i, H * W * Cc:]).reshape(H, W, self.planes)
+
+
 # ------------------------------------------------------------------------- runtime
 _RT = None
 
@@ -137,6 +252,10 @@ def runtime():
         'mlr_loader_start_epoch': ([vp, u64], i64),
         'mlr_loader_next': ([vp, vp], i32), 'mlr_loader_release': ([vp, i32], None),
         'mlr_loader_destroy': ([vp], None),
+        'mlr_seg_open': ([C.c_char_p], vp), 'mlr_seg_shape': ([vp, vp], None),
+        'mlr_seg_loader_create': ([vp, i32, i32, i32, i32, f64, f64, f64, f64, u64, i32, i32, i32, i32, i32, i32],
+                                  vp),
+        'mlr_seg_loader_set_slot': ([vp, i32, vp, vp, vp], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -167,7 +286,12 @@ def augment_reference(img: torch.Tensor, par: torch.Tensor, out_h: int, out_w: i
         top = g(iy0, ix0) + wx * (g(iy0, ix1) - g(iy0, ix0))
         bot = g(iy1, ix0) + wx * (g(iy1, ix1) - g(iy1, ix0))
         outs.append(top + wy * (bot - top))
-    x = torch.stack(outs)                                   # [B, oh, ow, C] in 0..255
+    return _normalise(torch.stack(outs), mean_istd, layout)
+
+
+def _normalise(x: torch.Tensor, mean_istd: Sequence[float], layout: str) -> torch.Tensor:
+    """[B, oh, ow, C] samples in 0..255 -> (x - mean) / std in ``layout``."""
+    Cc = x.shape[-1]
     mean = torch.tensor(mean_istd[:Cc])
     istd = torch.tensor(mean_istd[4:4 + Cc])
     x = (x - mean) * istd
@@ -179,6 +303,48 @@ def augment_reference(img: torch.Tensor, par: torch.Tensor, out_h: int, out_w: i
     return stem_s2d(x.to(torch.bfloat16), 3)
 
 
+def augment_seg_reference(img: torch.Tensor, mask: torch.Tensor, par: torch.Tensor, out_h: int, out_w: int,
+                          mean_istd: Sequence[float], layout: str = 'nchw', mask_kind: str = 'planes'):
+    """PyTorch twin of ``mlc_augment_seg``: img uint8 [B, H, W, C], mask uint8 [B, H, W, K],
+    par int [B, 8] (y0, x0, h, w, hflip, vflip, transpose, 0) -> (images in ``layout``,
+    masks: ``planes`` fp32 0/1 [B, oh, ow, K] in pixel order, ``index`` int64 [B, oh, ow]).
+
+    Output pixel (oy, ox) reads the box at row u of gh and column v of gw, where
+    (u, v, gh, gw) = (ox, oy, ow, oh) under transpose and (oy, ox, oh, ow) otherwise, then
+    hflip: v = gw-1-v and vflip: u = gh-1-u.  The image is the bilinear sample of
+    :func:`augment_reference` there; the mask is the nearest source pixel in integers,
+    row ((2u+1)*h) // (2*gh), column ((2v+1)*w) // (2*gw)."""
+    B, H, W, Cc = img.shape
+    p = par.long()
+    oy = torch.arange(out_h)[:, None].expand(out_h, out_w)
+    ox = torch.arange(out_w)[None, :].expand(out_h, out_w)
+    outs, mouts = [], []
+    for b in range(B):
+        y0, x0, h, w, hflip, vflip, tr = p[b, :7].tolist()
+        y0, x0 = min(max(y0, 0), H - 1), min(max(x0, 0), W - 1)      # the kernel clamps the box
+        h, w = min(max(h, 1), H - y0), min(max(w, 1), W - x0)        # into the image as well
+        u, v, gh, gw = (ox, oy, out_w, out_h) if tr else (oy, ox, out_h, out_w)
+        if hflip:
+            v = gw - 1 - v
+        if vflip:
+            u = gh - 1 - u
+        fy = ((u.float() + 0.5) * (h / gh) - 0.5).clamp(0, h - 1)
+        fx = ((v.float() + 0.5) * (w / gw) - 0.5).clamp(0, w - 1)
+        iy0, ix0 = fy.floor().long(), fx.floor().long()
+        iy1, ix1 = (iy0 + 1).clamp(max=h - 1), (ix0 + 1).clamp(max=w - 1)
+        wy, wx = (fy - iy0)[:, :, None], (fx - ix0)[:, :, None]
+        im = img[b].float()
+        g = lambda yy, xx: im[y0 + yy, x0 + xx]  # noqa: E731
+        top = g(iy0, ix0) + wx * (g(iy0, ix1) - g(iy0, ix0))
+        bot = g(iy1, ix0) + wx * (g(iy1, ix1) - g(iy1, ix0))
+        outs.append(top + wy * (bot - top))
+        row, col = ((2 * u + 1) * h) // (2 * gh), ((2 * v + 1) * w) // (2 * gw)
+        mouts.append(mask[b][y0 + row, x0 + col])
+    m = torch.stack(mouts)                                  # [B, oh, ow, K] uint8
+    m = m[..., 0].long() if mask_kind == 'index' else (m != 0).float()
+    return _normalise(torch.stack(outs), mean_istd, layout), m
+
+
 class RecordLoader:
     """Batches of a record file: dicts {'features', 'targets'} on ``device``.
 
@@ -188,14 +354,17 @@ class RecordLoader:
     ``train``) drops a last partial batch, otherwise it is completed by wrapping.
     ``threads`` host workers, ``depth`` pinned ring slots (>= 3)."""
 
-    def __init__(self, path: str, batch_size: int, out_size: int = 224, train: bool = True,
+    PAR = 5   # ints per sample in a slot's params
+
+    def __init__(self, path: str, batch_size: int, out_size=224, train: bool = True,
                  scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), seed: int = 0, rank: int = 0, world_size: int = 1,
                  shuffle: Optional[bool] = None, drop_last: Optional[bool] = None, threads: int = 8,
                  depth: int = 4, layout: str = 's2d', mean=IMAGENET_MEAN, std=IMAGENET_STD, device=None,
                  chunk: int = 16):
         self.path = path
         self.batch_size = int(batch_size)
-        self.out_h = self.out_w = int(out_size)
+        self.out_h, self.out_w = (int(v) for v in out_size) if isinstance(out_size, (tuple, list)) \
+            else (int(out_size), int(out_size))
         self.train = bool(train)
         self.layout = layout
         self.device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
@@ -203,13 +372,8 @@ class RecordLoader:
         self._explicit_epoch = False
         rt = runtime()
         self._rt = rt
-        self._file = rt.mlr_open(path.encode())
-        if not self._file:
-            raise ValueError(f'{path}: cannot open record file')
-        shp = (C.c_uint64 * 4)()
-        rt.mlr_shape(self._file, shp)
-        self.count, self.H, self.W, self.C = (int(v) for v in shp)
-        if layout not in LAYOUTS or (layout == 's2d' and (self.C != 3 or self.out_h % 2)):
+        self._open(path)
+        if layout not in LAYOUTS or (layout == 's2d' and (self.C != 3 or self.out_h % 2 or self.out_w % 2)):
             raise ValueError(f'layout {layout!r} does not fit {self.C}-channel images of {out_size}')
         ms = [0.0] * 8
         for c in range(min(self.C, 4)):
@@ -223,7 +387,7 @@ class RecordLoader:
         self._drop_last = bool(drop_last)
         self._live = None
         self._len = per // self.batch_size if drop_last else math.ceil(per / self.batch_size)
-        self._loader = rt.mlr_loader_create(self._file, self.batch_size, self.out_h, self.out_w, int(self.train),
+        self._loader = self._create(self._file, self.batch_size, self.out_h, self.out_w, int(self.train),
                                             float(scale[0]), float(scale[1]), float(ratio[0]), float(ratio[1]),
                                             int(seed), int(rank), int(world_size), int(shuffle), int(drop_last),
                                             int(threads), int(chunk))
@@ -234,17 +398,39 @@ class RecordLoader:
         self._slots = []
         for i in range(max(3, int(depth))):
             img = torch.empty(B, self.H, self.W, self.C, dtype=torch.uint8, pin_memory=pin)
-            lab = torch.empty(B, dtype=torch.int64, pin_memory=pin)
-            par = torch.empty(B, 5, dtype=torch.int32, pin_memory=pin)
-            rt.mlr_loader_set_slot(self._loader, i, C.c_void_p(img.data_ptr()), C.c_void_p(lab.data_ptr()),
-                                   C.c_void_p(par.data_ptr()))
+            lab = self._target_buffer(pin_memory=pin)
+            par = torch.empty(B, self.PAR, dtype=torch.int32, pin_memory=pin)
+            self._set_slot(self._loader, i, C.c_void_p(img.data_ptr()), C.c_void_p(lab.data_ptr()),
+                           C.c_void_p(par.data_ptr()))
             self._slots.append((img, lab, par))
         if self.device.type == 'cuda':
             self._copy_stream = torch.cuda.Stream(self.device)
-            self._dev = [(torch.empty(B, self.H, self.W, self.C, dtype=torch.uint8, device=self.device),
-                          torch.empty(B, 5, dtype=torch.int32, device=self.device)) for _ in range(2)]
+            self._dev = [self._staging() for _ in range(2)]
             self._ms_dev = torch.tensor(ms, dtype=torch.float32, device=self.device)
             self._used = [None, None]   # event: the augment kernel that last read each staging buffer
+
+    # what a segmentation loader does differently (SegRecordLoader)
+    def _open(self, path):
+        rt = self._rt
+        self._file = rt.mlr_open(path.encode())
+        if not self._file:
+            raise ValueError(f'{path}: cannot open record file')
+        shp = (C.c_uint64 * 4)()
+        rt.mlr_shape(self._file, shp)
+        self.count, self.H, self.W, self.C = (int(v) for v in shp)
+        self._create, self._set_slot = rt.mlr_loader_create, rt.mlr_loader_set_slot
+
+    def _target_buffer(self, **kw):
+        return torch.empty(self.batch_size, dtype=torch.int64, **kw)
+
+    def _staging(self):
+        B = self.batch_size
+        return (torch.empty(B, self.H, self.W, self.C, dtype=torch.uint8, device=self.device),
+                torch.empty(B, self.PAR, dtype=torch.int32, device=self.device))
+
+    def _augment_cpu(self, slot):
+        img, lab, par = slot
+        return augment_reference(img, par, self.out_h, self.out_w, self.mean_istd, self.layout), lab.clone()
 
     # the sampler-like API the runner calls
     @property
@@ -329,9 +515,7 @@ class RecordLoader:
                 if self.device.type == 'cuda':
                     x, y, done = self._augment_gpu(k, slot)
                 else:
-                    img, lab, par = slot
-                    x = augment_reference(img, par, self.out_h, self.out_w, self.mean_istd, self.layout)
-                    y = lab.clone()
+                    x, y = self._augment_cpu(slot)
                     done = None
                     rt.mlr_loader_release(self._loader, s)
                     s = -1
@@ -353,6 +537,9 @@ class RecordLoader:
             self._explicit_epoch = False
 
     def close(self):
+        prev = self._live() if getattr(self, '_live', None) is not None else None
+        if prev is not None:    # a live iterator hands its slot back before the loader goes
+            prev.close()
         if getattr(self, '_loader', None):
             self._rt.mlr_loader_destroy(self._loader)
             self._loader = None
@@ -367,4 +554,87 @@ class RecordLoader:
             pass
 
 
-__all__ = ['write_records', 'pack_images', 'RecordFile', 'RecordLoader', 'augment_reference', 'runtime']
+class SegRecordLoader(RecordLoader):
+    """Batches of an image + mask record file, on the ring, copy stream and events of
+    :class:`RecordLoader`.
+
+    ``train``: RandomResizedCrop(scale, ratio) + independent hflip / vflip / transpose coins,
+    one transform for the image (bilinear) and its mask (nearest); otherwise the centre crop.
+    ``out_size`` is an int or ``(h, w)``.  ``features`` come in ``layout``.  ``targets``:
+    ``planes`` files give float 0/1 masks, ``[B, K, h, w]`` for ``mask_order='nkhw'`` (what
+    torch criteria and the native eval path take) or pixel order ``[B, h, w, K]`` for
+    ``'pixel'`` (what ``NativeSegmentationStep.load_batch(..., pixel_order=True)`` copies
+    straight into its static buffer); ``index`` files give int64 class ids ``[B, h, w]``."""
+
+    PAR = 8
+
+    def __init__(self, path: str, batch_size: int, out_size=256, train: bool = True, scale=(0.5, 1.0),
+                 ratio=(3 / 4, 4 / 3), layout: str = 'nchw', mask_order: str = 'nkhw', **kw):
+        if mask_order not in ('nkhw', 'pixel'):
+            raise ValueError(f'mask_order: nkhw / pixel, not {mask_order!r}')
+        self.mask_order = mask_order
+        super().__init__(path, batch_size, out_size=out_size, train=train, scale=scale, ratio=ratio,
+                         layout=layout, **kw)
+
+    def _open(self, path):
+        rt = self._rt
+        self._file = rt.mlr_seg_open(path.encode())
+        if not self._file:
+            raise ValueError(f'{path}: cannot open image + mask record file')
+        shp = (C.c_uint64 * 6)()
+        rt.mlr_seg_shape(self._file, shp)
+        self.count, self.H, self.W, self.C, self.K, kind = (int(v) for v in shp)
+        self.mask_kind = 'index' if kind else 'planes'
+        self._create, self._set_slot = rt.mlr_seg_loader_create, rt.mlr_seg_loader_set_slot
+
+    def _target_buffer(self, **kw):
+        return torch.empty(self.batch_size, self.H, self.W, self.K, dtype=torch.uint8, **kw)
+
+    def _staging(self):
+        img, par = super()._staging()
+        return img, self._target_buffer(device=self.device), par
+
+    def _order(self, m):
+        if self.mask_kind == 'planes' and self.mask_order == 'nkhw':
+            return m.permute(0, 3, 1, 2).contiguous()
+        return m
+
+    def _augment_cpu(self, slot):
+        img, mask, par = slot
+        x, m = augment_seg_reference(img, mask, par, self.out_h, self.out_w, self.mean_istd, self.layout,
+                                     self.mask_kind)
+        return x, self._order(m)
+
+    def _augment_gpu(self, k, slot):
+        from mlcomp_amd.ops import _lib
+        img, mask, par = slot
+        dimg, dmask, dpar = self._dev[k % 2]
+        cur = torch.cuda.current_stream(self.device)
+        cs = self._copy_stream
+        if self._used[k % 2] is not None:
+            cs.wait_event(self._used[k % 2])
+        with torch.cuda.stream(cs):
+            dimg.copy_(img, non_blocking=True)
+            dmask.copy_(mask, non_blocking=True)
+            dpar.copy_(par, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(cs)
+        cur.wait_event(done)
+        B = self.batch_size
+        shape, dt = self._out_shape(B)
+        out = torch.empty(shape, dtype=dt, device=self.device)
+        if self.mask_kind == 'index':
+            m = torch.empty(B, self.out_h, self.out_w, dtype=torch.int64, device=self.device)
+        else:
+            m = torch.empty(B, self.out_h, self.out_w, self.K, dtype=torch.float32, device=self.device)
+        _lib.call('mlc_augment_seg', _lib.ptr(dimg), _lib.ptr(dmask), _lib.ptr(dpar), _lib.ptr(self._ms_dev),
+                  _lib.ptr(out), _lib.ptr(m), B, self.H, self.W, self.C, self.K, self.out_h, self.out_w,
+                  LAYOUTS[self.layout], MASK_KINDS[self.mask_kind], _lib.stream())
+        used = torch.cuda.Event()
+        used.record(cur)
+        self._used[k % 2] = used
+        return out, self._order(m), done
+
+
+__all__ = ['write_records', 'pack_images', 'RecordFile', 'RecordLoader', 'augment_reference', 'runtime',
+           'write_seg_records', 'pack_seg_images', 'SegRecordFile', 'SegRecordLoader', 'augment_seg_reference']

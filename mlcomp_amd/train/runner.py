@@ -271,7 +271,12 @@ class Runner:
         if self.native_kind == 'unet':
             from .native_seg_step import NativeSegmentationStep
             x = batch['features']
-            size = x.shape[1] if x.dtype == torch.bfloat16 and x.shape[-1] == 8 else x.shape[-1]
+            if x.dtype == torch.bfloat16 and x.shape[-1] == 16:     # stem space-to-depth image (pad 3)
+                size = 2 * x.shape[1] - 6
+            elif x.dtype == torch.bfloat16 and x.shape[-1] == 8:    # NHWC, channels padded to 8
+                size = x.shape[1]
+            else:
+                size = x.shape[-1]
             self.native_step = NativeSegmentationStep(
                 torch_model=self.model, batch=x.shape[0], image_size=size, device=self.device,
                 world_size=self.world_size, use_graph=use_graph, **plan)
@@ -340,7 +345,14 @@ class Runner:
         """``dataset: records``: the native input pipeline over ``path`` (train) and
         ``valid_path`` record files (:mod:`mlcomp_amd.train.records`); the native engine
         gets the stem's space-to-depth image straight from the augment kernel."""
-        from .records import RecordLoader
+        from .records import SEG_MAGIC, RecordLoader
+        try:
+            with open(dp['path'], 'rb') as f:
+                seg_file = f.read(8) == SEG_MAGIC
+        except OSError:     # the loader below reports a file it cannot open
+            seg_file = False
+        if dp.get('kind', 'segmentation' if seg_file else 'classification') == 'segmentation':
+            return self._seg_record_loaders(dp, bs)
         layout = 's2d' if self.state.native and self.native_kind == 'resnet' else 'nchw'
         common = dict(out_size=int(dp.get('image_size', 224)), rank=self.rank, world_size=self.world_size,
                       threads=int(dp.get('num_workers', 8) or 8), layout=layout, device=self.device,
@@ -351,6 +363,39 @@ class Runner:
         if dp.get('valid_path'):
             out['valid'] = RecordLoader(dp['valid_path'], bs, train=False, **common)
         return out
+
+    def _seg_record_loaders(self, dp, bs) -> 'OrderedDict[str, object]':
+        """``dataset: records`` over image + mask files (``kind: segmentation``, or told
+        from the file header).  A native segmentation stage gets the images in the layout its
+        stem reads and the training masks in pixel order, what the step's static buffers
+        hold; the torch and generic engines get NCHW fp32 images and [B, K, H, W] float
+        (``planes``) or [B, H, W] int64 (``index``) masks.  Validation masks stay
+        [B, K, H, W] on every engine: the native eval path takes them as they are."""
+        from .records import SegRecordLoader
+        native = self.state.native and self.native_kind == 'unet'
+        layout = 'nchw'
+        if native:
+            layout = 's2d' if self._seg_stem_s2d() else 'nhwc8'
+        size = dp.get('image_size', 256)
+        size = tuple(int(v) for v in size) if isinstance(size, (list, tuple)) else int(size)
+        common = dict(out_size=size, rank=self.rank, world_size=self.world_size,
+                      threads=int(dp.get('num_workers', 8) or 8), layout=layout, device=self.device,
+                      seed=int(dp.get('seed', 0)))
+        out = OrderedDict()
+        out['train'] = SegRecordLoader(dp['path'], bs, train=True, scale=tuple(dp.get('scale', (0.5, 1.0))),
+                                       ratio=tuple(dp.get('ratio', (3 / 4, 4 / 3))),
+                                       mask_order='pixel' if native else 'nkhw', **common)
+        if dp.get('valid_path'):
+            out['valid'] = SegRecordLoader(dp['valid_path'], bs, train=False, **common)
+        return out
+
+    def _seg_stem_s2d(self) -> bool:
+        """Whether the native engine of this stage's model reads the space-to-depth stem
+        image: the rule of ``lower_resnet_body(s2d_stem=True)`` (a 3-channel 7x7 / 2 stem)."""
+        for m in self.model.modules():
+            if isinstance(m, torch.nn.Conv2d):
+                return tuple(m.weight.shape[1:]) == (3, 7, 7) and m.stride[0] == 2 and m.padding[0] == 3
+        return False
 
     def _callbacks(self, stage) -> List[Callback]:
         cbs = OrderedDict(self.experiment.get_callbacks(stage))
@@ -476,7 +521,8 @@ class Runner:
                     count += st.batch_size
                     continue
                 if self.native_kind == 'unet':
-                    ns.load_batch(batch['features'], batch['targets'])
+                    ns.load_batch(batch['features'], batch['targets'],
+                                  pixel_order=getattr(loader, 'mask_order', None) == 'pixel')
                     ns()
                     st.batch_size = ns.batch
                     if dev_loss is None:
