@@ -1114,6 +1114,66 @@ struct EpiF32 {  // fp32 [M][ld] = acc (+ bias[n]) (+= if accumulate)
   }
 };
 
+// Inference epilogue: out[m][n] = act(acc + bias[n] + addend[m][n]), summed in fp32 from the
+// accumulators and rounded to bf16 once (EpiBF16's dense form rounds the accumulator first
+// and adds its addend after the activation).  A BN-folded conv unit ends here: bias is the
+// folded shift, addend the block's shortcut.  The addend tile (exactly the BMxBN output
+// tile, rows of lda elements) is read 16 B/lane into the staging image the stores leave
+// from; each lane then picks up the elements of its own accumulators there and writes the
+// result back in place, so an element is only ever touched by the lane that owns it.
+struct EpiRes {
+  bf16* out; int ld; const float* bias; const bf16* addend; int lda; int relu;
+  template <int BM, int BN, int MI, int NI>
+  __device__ void apply(f32x16 (&acc)[MI][NI], char* lds, int m0, int n0, int M, int N,
+                        int wm, int wn, int lane, int tid) const {
+    constexpr int RS = (BN + 8) * 2;
+    constexpr int CPR = BN / 8;              // 16 B chunks per row
+    constexpr int RPI = NTHR / CPR;          // rows per iteration
+    static_assert(RPI * CPR == NTHR && BM % RPI == 0, "EpiRes: tiles of launch_tiles only");
+    constexpr int ITERS = BM / RPI;
+    const int c = tid % CPR, r0 = tid / CPR;
+    const int nc = n0 + c * 8;
+    const bool has_add = addend != nullptr;   // block-uniform
+    __syncthreads();
+    if (has_add) {
+#pragma unroll
+      for (int it = 0; it < ITERS; ++it) {
+        const int row = r0 + RPI * it;
+        const int m = m0 + row;
+        // rows / columns outside the output: element 0 (valid), never stored
+        const size_t off = (m < M && nc < N) ? (size_t)m * lda + nc : 0;
+        *reinterpret_cast<uint4*>(lds + row * RS + c * 16) = ldg16(addend + off);
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int j = 0; j < NI; ++j) {
+      const int nl = wn * 32 * NI + 32 * j + (lane & 31);
+      const float b = (bias && n0 + nl < N) ? bias[n0 + nl] : 0.f;
+#pragma unroll
+      for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int ml = wm * 32 * MI + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+          bf16* p = reinterpret_cast<bf16*>(lds + ml * RS + nl * 2);
+          float v = acc[i][j][r] + b;
+          if (has_add) v += (float)*p;
+          if (relu) v = fmaxf(v, 0.f);
+          *p = (bf16)v;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < ITERS; ++it) {
+      const int row = r0 + RPI * it;
+      const int m = m0 + row;
+      if (m < M && nc < N)
+        *reinterpret_cast<uint4*>(out + (size_t)m * ld + nc) =
+            *reinterpret_cast<const uint4*>(lds + row * RS + c * 16);
+    }
+  }
+};
+
 // ---------------------------------------------------------------- main loop
 // PF = 1: the next K-tile's loads are issued before the MFMAs of the current one.
 // PF = 2: two register sets, loads issued two K-tiles ahead (the last tiles' prefetches
@@ -2166,6 +2226,25 @@ MLC_EXPORT int mlc_conv_fwd_ex(const bf16* x, const bf16* w, bf16* y, const floa
   EpiBF16<IdentityRows, true> epi{y, Co, nullptr, nullptr, IdentityRows{}, nullptr};
   epi.bias = bias;
   epi.act = act;
+  const MkMatKC fb{w, K, Co, K};
+  if (KH == 1 && KW == 1 && stride == 1 && pad == 0)
+    return launch_tiles(tile, M, Co, K, 1, st, epi, MkMatKC{x, C, M, K}, fb);
+  const ConvGeom g = mkgeom(N, H, W, C, Co, KH, KW, stride, pad, dil, Ho, Wo);
+  return launch_tiles(tile, M, Co, K, 1, st, epi, MkConvFwdA{x, g, M, K}, fb);
+}
+
+// Inference conv unit: z = act(conv(x, w) + bias + addend) in one pass (EpiRes; act 0 or
+// 3 = ReLU).  bias ([Co] fp32) and addend (bf16 [M][Co], rows of lda >= Co elements, lda % 8
+// == 0, 16-byte aligned) are both optional.  With BatchNorm folded into w and bias this is
+// a whole conv-BN(-add)(-ReLU) unit; addend is a bottleneck's shortcut.
+MLC_EXPORT int mlc_conv_fwd_res(const bf16* x, const bf16* w, bf16* y, const float* bias, int act,
+                                const bf16* addend, int lda, int N, int H, int W, int C, int Co, int KH, int KW,
+                                int stride, int pad, int dil, int Ho, int Wo, hipStream_t st) {
+  if (C % 8 || Co % 8 || KH > 15 || KW > 16 || (act != 0 && act != 3)) return -1;
+  if (addend && (lda < Co || lda % 8)) return -1;
+  const int M = N * Ho * Wo, K = KH * KW * C;
+  const int tile = pick_tile(M, Co);
+  const EpiRes epi{y, Co, bias, addend, lda, act == 3};
   const MkMatKC fb{w, K, Co, K};
   if (KH == 1 && KW == 1 && stride == 1 && pad == 0)
     return launch_tiles(tile, M, Co, K, 1, st, epi, MkMatKC{x, C, M, K}, fb);

@@ -22,8 +22,13 @@ def _default_transform(size=224, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 
 
 def infer(files: List[str], checkpoint: str, model=None, class_: str = 'Pretrained', variant: str = 'resnet34',
           activation: str = 'softmax', num_classes: int = 2, batch_size: int = 16, device: str = None,
-          transforms=None) -> np.ndarray:
+          transforms=None, engine: str = 'torch') -> np.ndarray:
+    """``engine``: 'torch' (default; bf16 autocast), 'native' (the hand-written kernels through
+    :class:`~mlcomp_amd.train.native_infer.NativeInference`; raises when the model has no native
+    lowering) or 'auto' (native when possible, else torch with the reason logged)."""
     assert activation in ('softmax', 'sigmoid', None)
+    if engine not in ('torch', 'native', 'auto'):
+        raise ValueError(f'engine: torch / native / auto, not {engine!r}')
     from mlcomp_amd.contrib.dataset import read_image_file
     from mlcomp_amd.models import build_model
     device = device or ('cuda' if torch.cuda.is_available() else 'cpu')
@@ -39,9 +44,27 @@ def infer(files: List[str], checkpoint: str, model=None, class_: str = 'Pretrain
     except RuntimeError:   # checkpoint of the bare backbone inside a Pretrained wrapper
         model.model.load_state_dict(sd)
     model = model.to(device).eval()
+    use_native, native_engine = False, None
+    if engine != 'torch':
+        from mlcomp_amd.train.native_infer import NO_DEVICE, NativeInference, unsupported_reason
+        reason = NO_DEVICE if torch.device(device).type != 'cuda' else unsupported_reason(model)
+        if reason is not None and engine == 'native':
+            raise RuntimeError(f'engine: native cannot run this model: {reason}')
+        if reason is not None:
+            import logging
+            logging.getLogger(__name__).warning('engine: auto runs the torch path: %s', reason)
+        use_native = reason is None
     preds = []
     for i in range(0, len(files), batch_size):
         batch = np.stack([transforms(image=read_image_file(f))['image'] for f in files[i:i + batch_size]])
+        if use_native:
+            if native_engine is None:      # built at the first batch, when the image size is known
+                native_engine = NativeInference(model, batch_size, batch.shape[2:], device=device)
+            p = native_engine.predict(torch.from_numpy(batch).float())
+            with torch.no_grad():
+                p = torch.softmax(p, 1) if activation == 'softmax' else torch.sigmoid(p) if activation else p
+            preds.append(p.cpu().numpy())
+            continue
         with torch.no_grad(), torch.autocast(device if device != 'cpu' else 'cpu', dtype=torch.bfloat16,
                                              enabled=device != 'cpu'):
             p = model(torch.from_numpy(batch).to(device)).float()

@@ -139,6 +139,7 @@ _SIGS = {
     'mlc_chscale_fwd': [vp] * 4 + [i32, i64, i32, i32, vp],
     'mlc_chscale_bwd': [vp] * 8 + [i32] * 3 + [vp],
     'mlc_conv_fwd_ex': [vp] * 4 + [i32] * 13 + [vp],
+    'mlc_conv_fwd_res': [vp] * 4 + [i32, vp] + [i32] * 13 + [vp],
     'mlc_conv_wgrad_bias': [vp] * 4 + [i32] * 13 + [vp, i64, vp],
     'mlc_temporal_unfold': [vp, vp] + [i32] * 9 + [vp],
     'mlc_temporal_fold': [vp, vp, vp] + [i32] * 9 + [vp],

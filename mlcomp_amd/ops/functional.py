@@ -1325,6 +1325,41 @@ def conv2d_fwd_ex(x, w, bias=None, act=0, stride=1, pad=0, dil=1):
     return yf.permute(0, 2, 3, 1).to(torch.bfloat16).contiguous()
 
 
+def conv2d_fwd_res(x, w, bias=None, addend=None, act=0, stride=1, pad=0, dil=1):
+    """z = act(conv(x, w) + bias + addend), summed in fp32 and rounded to bf16 once (act 0 or
+    3 = ReLU) - an inference conv unit with BatchNorm folded into ``w`` / ``bias`` and the
+    block's shortcut as ``addend`` ([N, Ho, Wo, Co] bf16; may be the leading channels of wider
+    rows).  groups == 1."""
+    N, H, W, C = x.shape
+    Co, KH, KW, Ci = w.shape
+    assert Ci == C, (w.shape, x.shape)
+    assert act in (0, 3), act
+    Ho, Wo = conv_out_hw(H, W, KH, KW, stride, pad, dil)
+    if addend is not None:
+        assert tuple(addend.shape) == (N, Ho, Wo, Co) and addend.dtype == torch.bfloat16, (addend.shape, addend.dtype)
+    if _cuda(x):
+        # the kernel reads raw pointers: dense bf16 operands and an fp32 bias, all on x's device
+        assert x.dtype == torch.bfloat16 and x.is_contiguous(), (x.dtype, x.stride())
+        assert w.dtype == torch.bfloat16 and w.is_contiguous() and w.device == x.device, (w.dtype, w.stride(), w.device)
+        assert bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.device == x.device
+                                and bias.numel() == Co), (bias.dtype, bias.shape, bias.device)
+        assert addend is None or addend.device == x.device, addend.device
+        lda = 0
+        if addend is not None:
+            lda = rows_ld(addend)
+            assert lda is not None and lda % 8 == 0 and addend.data_ptr() % 16 == 0, (addend.shape, addend.stride())
+        y = torch.empty(N, Ho, Wo, Co, device=x.device, dtype=torch.bfloat16)
+        _lib.call('mlc_conv_fwd_res', _lib.ptr(x), _lib.ptr(w), _lib.ptr(y), _lib.ptr(bias), int(act),
+                  _lib.ptr(addend), lda, N, H, W, C, Co, KH, KW, stride, pack_pad(pad), dil, Ho, Wo, _lib.stream())
+        return y
+    yf = F.conv2d(_nchw(x), w.permute(0, 3, 1, 2).float(), bias, stride, pad, dil).permute(0, 2, 3, 1)
+    if addend is not None:
+        yf = yf + addend.float()
+    if act == 3:
+        yf = yf.clamp_min(0)
+    return yf.to(torch.bfloat16).contiguous()
+
+
 def conv2d_wgrad_bias(dy, x, w_shape, dbias, stride=1, pad=0, dil=1, out=None, accumulate=False, slab=None):
     """fp32 weight gradient [Co, KH, KW, Ci] and dbias[Co] += colsum(dy), one GEMM."""
     Co, KH, KW, Ci = w_shape

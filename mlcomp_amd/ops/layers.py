@@ -98,6 +98,10 @@ class NativeContext:
         # split-K conv weight gradients through fp32 slabs + a reduce pass (True) or straight
         # fp32 atomics (False); engines pick their measured default, MLC_WGRAD_SLAB overrides
         self.wgrad_slab = os.environ.get('MLC_WGRAD_SLAB', '1') != '0'
+        # deploy (inference engines opt in; eval mode only): a ConvBN unit runs as one conv
+        # whose weights and bias carry the BatchNorm (ConvBN.refold) and whose epilogue adds
+        # the shortcut and applies the ReLU - no pre-BN tensor, no BN-apply pass
+        self.deploy = False
 
     def default_wgrad_slab(self, on: bool):
         """Engine default for the conv weight-gradient split-K reduction (MLC_WGRAD_SLAB
@@ -281,6 +285,14 @@ class ConvBN:
         if isinstance(res, tuple):
             res, rs, rh = res
             raff = (rs, rh)
+        if not self.ctx.training and self.ctx.deploy and self.folds():
+            assert raff is None and in_affine is None and not defer, \
+                f'{self.name}: deploy mode takes a materialised residual and input'
+            if self._fold is None:
+                self.refold()
+            w_fold, b_fold = self._fold
+            z = Fn.conv2d_fwd_res(x, w_fold, b_fold, res, 3 if self.act else 0, self.stride, self.pad, self.dil)
+            return z, (x, None, z)
         if not self.ctx.training:  # inference BN: running statistics, no stat epilogue
             y = self._conv(x, None, in_affine)
             torch.rsqrt(self.run_var + self.eps, out=self.scale).mul_(self.gamma.master)
@@ -298,6 +310,33 @@ class ConvBN:
                             self.run_var if training else None, self.eps, self.momentum, self.act,
                             scale=self.scale, shift=self.shift, res_affine=raff, apply=not defer)
         return z, (x, y, z)
+
+    _fold = None   # (w_fold bf16, b_fold fp32) of deploy mode, see refold()
+
+    def folds(self) -> bool:
+        """True for the units deploy mode runs as one folded conv: the plain convs.  The
+        space-to-depth stem and the transposed convs (ConvTBN) keep the unfolded eval path."""
+        return type(self) is ConvBN and not self.s2d
+
+    def refold(self):
+        """(Re)compute the deploy-mode operands from the current parameters and running
+        statistics: w_fold = bf16(w * scale[co]) with scale = gamma * rsqrt(var + eps), formed
+        in fp32 from the master weights and rounded once, and b_fold = beta - mean * scale.
+        They are cached; whoever changes the parameters calls this again, and a refresh writes
+        into the same two tensors.  (A checkpoint load through ``load_from_torch`` re-creates
+        the unit's statistics buffers, so NativeInference.load_state_dict also recaptures
+        its graph.)"""
+        if not self.folds():
+            return
+        with torch.no_grad():
+            scale = self.gamma.master.float() * torch.rsqrt(self.run_var.float() + self.eps)
+            w_fold = (self.w.master.float() * scale.view(-1, 1, 1, 1)).to(torch.bfloat16).contiguous()
+            b_fold = (self.beta.master.float() - self.run_mean.float() * scale).contiguous()
+            if self._fold is None:
+                self._fold = (w_fold, b_fold)
+            else:
+                self._fold[0].copy_(w_fold)
+                self._fold[1].copy_(b_fold)
 
     # the three GEMMs of the unit (overridden by ConvTBN)
     def _conv(self, x, stats, in_affine=None):
@@ -575,7 +614,19 @@ class ResidualBlock:
         return [None] + [(p.scale, p.shift) if f else None for p, f in zip(self.units[:-1], self.fuse_into[1:])]
 
     def __call__(self, x):
+        if self.ctx.deploy and not self.ctx.training:
+            return self.deploy_fwd(x)
         return _ResidualBlockFn.apply(x, self.ctx.anchor, self)
+
+    def deploy_fwd(self, x):
+        """Inference forward on folded units: one kernel per conv, the shortcut materialised
+        and added in the last unit's epilogue.  No deferred BN outputs, no loader transforms,
+        nothing kept for a backward."""
+        identity = x if self.down is None else self.down.fwd(x)[0]
+        y = x
+        for u in self.units[:-1]:
+            y = u.fwd(y)[0]
+        return self.units[-1].fwd(y, identity)[0]
 
     def output_bn_spec(self):
         """BnBwdSpec for the gradient of this block's output (used by the next block).

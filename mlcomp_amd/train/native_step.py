@@ -22,7 +22,7 @@ from mlcomp_amd.ops import functional as Fn
 from mlcomp_amd.ops.layers import flatten_bn_buffers
 from mlcomp_amd.parallel.comm import make_comm
 from mlcomp_amd.parallel.ddp import GradBucketer
-from mlcomp_amd.train.graphed import GraphedStep
+from mlcomp_amd.train.graphed import GraphedStep, work_stream
 from mlcomp_amd.train.optim import FusedAdam, FusedSGD
 
 
@@ -102,6 +102,18 @@ class NativeClassifierStep(GraphedStep):
             self.opt.step()
         self._end_of_step_buffers()
         self._loss = self.net.head.loss_sum()
+
+    def predict(self, x):
+        """fp32 logits of ``x`` (NCHW float or NHWC bf16) from the step's own net in eval mode:
+        running statistics, no autograd, the unfolded eval path."""
+        self.net.eval()
+        try:
+            with torch.no_grad(), work_stream(self.device):
+                if x.dim() == 4 and x.shape[1] in (1, 3) and x.dtype != torch.bfloat16:
+                    x = Fn.nchw_to_nhwc(x.to(self.device, non_blocking=True).float(), pad_to=STEM_CIN)
+                return self.net.logits(self._prep(x.to(self.device, non_blocking=True))).float()
+        finally:
+            self.net.train()
 
     def set_lr(self, lr):
         self.opt.set_lr(lr)
