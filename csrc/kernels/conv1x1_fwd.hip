@@ -20,7 +20,7 @@
 // the igemm fragments, so the accumulators and the stored y are bit-identical to igemm's.
 // Blocks that share rows (the Co / 256 chunks of one row group) are launched 8 ids apart, i.e.
 // on the same XCD, so the repeated reads of x meet in that XCD's L2.
-#include "common.h"
+#include "gfx950.h"
 
 namespace {
 
@@ -28,24 +28,9 @@ constexpr int NT = 256;      // 4 waves
 constexpr int BM = 64;       // rows per tile
 constexpr int CHUNK = 256;   // output channels per block (64 per wave)
 
-typedef __amdgpu_buffer_rsrc_t Rsrc;
-constexpr unsigned OOB = 0x80000000u;   // voffset past the range: a load returns 0, a store is dropped
-// `bytes` from `base` on: x / y from a tile's first row to the end of the tensor, so whatever
-// the offsets are, the hardware confines every access to the tensor
-__device__ __forceinline__ Rsrc rsrc(const void* base, long bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0,
-                                           (int)(bytes < 0x7ffffff0L ? bytes : 0x7ffffff0L), 0x00020000);
-}
-__device__ __forceinline__ uint4 bload(Rsrc r, unsigned voff) {
-  return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
-}
-// branch-free 16-byte store, dropped for an out-of-bounds voffset
-__device__ __forceinline__ void bstore(Rsrc r, unsigned voff, int imm, const uint4& v) {
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  __builtin_amdgcn_raw_buffer_store_b128(u32x4{v.x, v.y, v.z, v.w}, r, voff, imm, 0);
-}
-// raw barrier: __syncthreads() would also wait for the next tile's global loads (vmcnt(0))
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// x and y go through bounded buffer resources (gfx950.h) that span from a tile's first row to
+// the end of the tensor, so whatever the offsets are, the hardware confines every access to
+// the tensor
 
 struct FwdArgs {
   const bf16* x; const bf16* w; bf16* y; float* sum; float* sumsq;
@@ -86,7 +71,7 @@ __global__ void __launch_bounds__(NT, 1) conv1x1_fwd_kernel(const FwdArgs a) {
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int s = 0; s < KS; ++s)
-      wf[i][s] = __builtin_bit_cast(bf16x8, ldg16(a.w + (long)(cb + 32 * i + l32) * K + s * 16 + h * 8));
+      wf[i][s] = ldfrag(a.w + (long)(cb + 32 * i + l32) * K + s * 16 + h * 8);
 
   // per-lane statistics of channel cb + 32 i + (r & 3) + 8 (r >> 2) + 4 h over rows = l32 mod 32
   f32x16 s1[2], s2[2];

@@ -1,29 +1,14 @@
 // Convolution geometry shared by the implicit-GEMM engines (igemm.hip: 128x128 tiles,
-// gemm256.hip: 256-row LDS-DMA tiles): multiply-shift division, NHWC conv geometry, the
+// gemm256.hip: 256-row LDS-DMA tiles): NHWC conv geometry (divisions by FastDiv), the
 // per-row filter-tap masks and the stride-parity classes of a transposed (dgrad) conv.
 // The K axis of every conv GEMM is walked in 64-deep steps (one filter tap per step when
 // the channel count is a multiple of 64).
 #pragma once
-#include "common.h"
+#include "gfx950.h"
 
 namespace igemm {
 
 constexpr int NSTAT = 32;   // BN-statistic partial copies (spread same-address atomics)
-
-// ------------------------------------------------------------------ fast division
-struct FastDiv {
-  unsigned d, mul, sh;
-  __host__ __device__ FastDiv() : d(1), mul(0), sh(0) {}
-  __host__ explicit FastDiv(unsigned dd) : d(dd) {
-    sh = 0;
-    while ((1u << sh) < d) ++sh;
-    mul = (unsigned)((((unsigned long long)1 << 32) * ((1ull << sh) - d)) / d + 1);
-  }
-  __device__ __forceinline__ unsigned div(unsigned n) const { return (__umulhi(n, mul) + n) >> sh; }
-  __device__ __forceinline__ void divmod(unsigned n, unsigned& q, unsigned& r) const {
-    q = div(n); r = n - q * d;
-  }
-};
 
 // ---------------------------------------------------------------- geometry
 struct ConvGeom {
@@ -71,7 +56,6 @@ struct DgradClass {
 namespace igemm_host {
 using igemm::ConvGeom;
 using igemm::DgradClass;
-using igemm::FastDiv;
 
 // The conv exports take one int `pad`: a plain value pads both axes; (1 << 30) | (pad_w << 15)
 // | pad_h packs per-axis paddings (a 1x7 / 7x1 conv with padding (0, 3) / (3, 0)).

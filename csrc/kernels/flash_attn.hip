@@ -43,7 +43,7 @@
 // (ds_read_b128, the MFMA A/B fragment of one row) and the transposed reads are
 // conflict-free (checked with the bank model of MI355X_MICROARCH.md §LDS: D=128 is the
 // guide's dual-use image (b), D=64 a swizzle over row bits 1, 3, 4 found the same way).
-#include "common.h"
+#include "gfx950.h"
 #include "dropout.h"
 #include <stdlib.h>
 
@@ -76,13 +76,8 @@ __device__ __forceinline__ bf16x8 trf(const char* img, int base, int k0, int lan
   const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
   const int col = base + 16 * (g & 1) + 4 * p;
   const int kr = k0 + 8 * (g >> 1);
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (LDS_PTR(s16x4))(img + off<D>(kr + q, col >> 3) + (col & 7) * 2));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (LDS_PTR(s16x4))(img + off<D>(kr + 4 + q, col >> 3) + (col & 7) * 2));
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  const s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, r);
+  return tr_pair(tr_read(img + off<D>(kr + q, col >> 3) + (col & 7) * 2),
+                 tr_read(img + off<D>(kr + 4 + q, col >> 3) + (col & 7) * 2));
 }
 // K-contiguous fragment of row `row` straight from global (ld elements per row)
 __device__ __forceinline__ bf16x8 gfrag(const bf16* base, int ld, int row, int s, int lane) {

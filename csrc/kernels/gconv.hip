@@ -21,7 +21,7 @@
 // threads, as the BatchNorm passes) and walk pixels; the weight gradient reduces per
 // thread, then per block (LDS), then over 32 partial copies.
 #include <numeric>
-#include "common.h"
+#include "gfx950.h"
 #include <stdlib.h>
 
 namespace gconv {
@@ -42,10 +42,6 @@ struct GGeom {
 // first K-side channel (8-aligned) of the 16-channel output block starting at oc0: the block
 // spans the groups oc0/Cog .. (oc0+15)/Cog, whose K-side channels start at (oc0/Cog)*Cg
 __device__ __host__ __forceinline__ int blk_cbase(int oc0, int Cog, int Cg) { return (oc0 / Cog) * Cg & ~7; }
-
-__device__ __forceinline__ bf16x8 ldfrag(const bf16* p) {
-  return *reinterpret_cast<const bf16x8*>(p);
-}
 
 // ------------------------------------------------------------------ weight expansion
 // WB[ob][j][k] (k < Kp): the B operand of the 16-column output block ob.  tr = 0: the
@@ -197,27 +193,19 @@ struct TGeom {
 
 __host__ __device__ __forceinline__ int floordiv(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 
-__device__ __forceinline__ int tb_off(int pix, int c) { return pix * 128 + ((c ^ ((pix >> 1) & 7)) << 4); }
-
-// LDS-DMA staging (buffer_load ... lds, no VGPR round trip, every load of the stage in flight
-// at once): `npix` staged pixels of 128-byte slab rows into `img` in the tb_off layout.  A
-// wave instruction fills 8 consecutive pixel rows (1 KB, lane-linear), so the swizzle moves to
-// the source side: lane l fetches logical chunk (l & 7) ^ ((P >> 1) & 7) of pixel P.  voff(P, c)
-// is that chunk's byte offset from the resource base, or TB_OOB for zeros (padding).
-typedef __amdgpu_buffer_rsrc_t TRsrc;
-constexpr unsigned TB_OOB = 0x80000000u;
-__device__ __forceinline__ TRsrc tb_rsrc(const void* base) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, 0x7ffffff0, 0x00020000);
-}
+// LDS-DMA staging (every load of the stage in flight at once): `npix` staged pixels of
+// 128-byte slab rows into `img` in the kc_off layout (row = staged pixel).  A wave instruction
+// fills 8 consecutive pixel rows (1 KB, lane-linear), so the swizzle moves to the source side:
+// lane l fetches logical chunk c = (l & 7) ^ kc_swz(P) of pixel P.  voff(P, c) is that chunk's
+// byte offset from the resource base, or OOB for zeros (padding).
 template <class F>
-__device__ __forceinline__ void tb_dma(char* img, int npix, TRsrc rs, F voff) {
+__device__ __forceinline__ void tb_dma(char* img, int npix, Rsrc rs, F voff) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   char* dst0 = img + __builtin_amdgcn_readfirstlane(wave) * 1024;
   for (int r = 0; r * 32 < npix; ++r) {
-    const int P = r * 32 + wave * 8 + (lane >> 3), c = (lane & 7) ^ ((P >> 1) & 7);
-    const unsigned vo = P < npix ? voff(P, c) : TB_OOB;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(dst0 + r * 4096), 16, vo,
-                                             0, 0, 0);
+    const int P = r * 32 + wave * 8 + (lane >> 3), c = (lane & 7) ^ kc_swz(P);
+    const unsigned vo = P < npix ? voff(P, c) : OOB;
+    dma16(rs, dst0 + r * 4096, vo);
   }
 }
 
@@ -236,12 +224,12 @@ gconv_band_kernel(const bf16* __restrict__ in, const bf16* __restrict__ wb, bf16
   const int hi0 = MODE == 2 ? floordiv(oh0 + g.P - (g.KH - 1) * g.D, g.S) : oh0 * g.S - g.P;
   // ---- stage the slab's input rows hi0 .. hi0+rows_in-1, columns wc0 .. wc0+Wp-1 (zeros outside)
   {
-    const TRsrc rs = tb_rsrc(in + (long)n * g.Hi * g.Wi * g.C + cs0);
+    const Rsrc rs = rsrc(in + (long)n * g.Hi * g.Wi * g.C + cs0);
     tb_dma(lds, g.rows_in * g.Wp, rs, [&](int pix, int c) -> unsigned {
       const int ir = pix / g.Wp, ic = pix - ir * g.Wp;
       const int hi = hi0 + ir, wi = ic + g.wc0;
       return (unsigned)hi < (unsigned)g.Hi && (unsigned)wi < (unsigned)g.Wi
-                 ? (unsigned)((hi * g.Wi + wi) * g.C + 8 * c) * 2u : TB_OOB;
+                 ? (unsigned)((hi * g.Wi + wi) * g.C + 8 * c) * 2u : OOB;
     });
   }
   // ---- B fragments of this wave's 16-channel output block (all K-steps, registers)
@@ -276,7 +264,7 @@ gconv_band_kernel(const bf16* __restrict__ in, const bf16* __restrict__ wb, bf16
       tch[ks] = 0;
     }
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this thread's DMA (and B loads) landed
+  vmwait<0>();   // this thread's DMA (and B loads) landed
   __syncthreads();
   // ---- MFMA rows of 16 output pixels (flattened over the band's rows)
   const int nrow = (npx + 15) / 16;
@@ -298,9 +286,9 @@ gconv_band_kernel(const bf16* __restrict__ in, const bf16* __restrict__ wb, bf16
             const int nh = ro - toff[ks], nw = co - tcol[ks];
             const int qh = g.S == 2 ? nh >> 1 : nh / g.S, qw = g.S == 2 ? nw >> 1 : nw / g.S;
             if (toff[ks] >= 0 && qh * g.S == nh && qw * g.S == nw)
-              a = *reinterpret_cast<const bf16x8*>(lds + tb_off(qh * g.Wp + qw, tch[ks]));
+              a = *reinterpret_cast<const bf16x8*>(lds + kc_off(qh * g.Wp + qw, tch[ks]));
           } else if (toff[ks] >= 0) {
-            a = *reinterpret_cast<const bf16x8*>(lds + tb_off(base + toff[ks], tch[ks]));
+            a = *reinterpret_cast<const bf16x8*>(lds + kc_off(base + toff[ks], tch[ks]));
           }
           acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bfr[ks], acc[m], 0, 0, 0);
         }
@@ -333,7 +321,7 @@ gconv_band_kernel(const bf16* __restrict__ in, const bf16* __restrict__ wb, bf16
       for (int i = 0; i < 4; ++i) {
         const int q = 16 * m + 4 * hl + i;
         const int ch = 16 * ob + j;
-        *reinterpret_cast<bf16*>(lds + tb_off(q, ch >> 3) + (ch & 7) * 2) = (bf16)acc[m][i];
+        *reinterpret_cast<bf16*>(lds + kc_off(q, ch >> 3) + (ch & 7) * 2) = (bf16)acc[m][i];
       }
     }
   }
@@ -341,7 +329,7 @@ gconv_band_kernel(const bf16* __restrict__ in, const bf16* __restrict__ wb, bf16
   bf16* ob_base = out + ((long)n * g.Ho + oh0) * g.Wo * g.C + cs0;
   for (int i = tid; i < npx * 8; i += NT) {
     const int q = i >> 3, c = i & 7;
-    *reinterpret_cast<uint4*>(ob_base + (long)q * g.C + 8 * c) = *reinterpret_cast<const uint4*>(lds + tb_off(q, c));
+    *reinterpret_cast<uint4*>(ob_base + (long)q * g.C + 8 * c) = *reinterpret_cast<const uint4*>(lds + kc_off(q, c));
   }
 }
 
@@ -395,16 +383,10 @@ inline void launch_band(const TGeom& t, int N, int KB, const bf16* in, const bf1
 // block) runs K = 32 pixels per MFMA with both operands read transposed (ds_read_b64_tr_b16,
 // as gconv_wgrad_kernel's tr_frag, from the swizzled 128-byte pixel rows); the T x KB/16
 // accumulator tiles stay in registers over the whole run, then one atomic per in-group weight.
-typedef short s16x4b __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ bf16x8 band_tr_frag(const char* lds, int pa, int pb, int ch) {
   // lane rows pa (8g+q) and pb (8g+4+q), channels ch..ch+3 (ch % 4 == 0)
   const int within = (ch & 7) * 2;
-  const s16x4b lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4b))(lds + tb_off(pa, ch >> 3) + within));
-  const s16x4b hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4b))(lds + tb_off(pb, ch >> 3) + within));
-  typedef short s16x8b __attribute__((ext_vector_type(8)));
-  const s16x8b r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, r);
+  return tr_pair(tr_read(lds + kc_off(pa, ch >> 3) + within), tr_read(lds + kc_off(pb, ch >> 3) + within));
 }
 
 template <int KB>
@@ -436,16 +418,16 @@ gconv_band_wgrad_kernel(const bf16* __restrict__ dy, const bf16* __restrict__ x,
     const int rows = min(g.R, g.Ho - oh0), npx = rows * g.Wo, npx32 = (npx + 31) & ~31;
     const int hi0 = oh0 * g.S - g.P;
     __syncthreads();   // the previous band's LDS reads are done
-    tb_dma(ldx, g.rows_in * g.Wp, tb_rsrc(x + (long)n * g.Hi * g.Wi * g.C + cs0), [&](int pix, int c) -> unsigned {
+    tb_dma(ldx, g.rows_in * g.Wp, rsrc(x + (long)n * g.Hi * g.Wi * g.C + cs0), [&](int pix, int c) -> unsigned {
       const int ir = pix / g.Wp, ic = pix - ir * g.Wp;
       const int hi = hi0 + ir, wi = ic + g.wc0;
       return (unsigned)hi < (unsigned)g.Hi && (unsigned)wi < (unsigned)g.Wi
-                 ? (unsigned)((hi * g.Wi + wi) * g.C + 8 * c) * 2u : TB_OOB;
+                 ? (unsigned)((hi * g.Wi + wi) * g.C + 8 * c) * 2u : OOB;
     });
-    tb_dma(ldy, npx32, tb_rsrc(dy + ((long)n * g.Ho + oh0) * g.Wo * g.C + cs0), [&](int q, int c) -> unsigned {
-      return q < npx ? (unsigned)(q * g.C + 8 * c) * 2u : TB_OOB;
+    tb_dma(ldy, npx32, rsrc(dy + ((long)n * g.Ho + oh0) * g.Wo * g.C + cs0), [&](int q, int c) -> unsigned {
+      return q < npx ? (unsigned)(q * g.C + 8 * c) * 2u : OOB;
     });
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vmwait<0>();
     __syncthreads();
     for (int px0 = 0; px0 < npx32; px0 += 32) {
       const int ra = px0 + 8 * gq + qq, rb = ra + 4;
@@ -489,19 +471,13 @@ gconv_band_wgrad_kernel(const bf16* __restrict__ dy, const bf16* __restrict__ x,
 // selects which), a pixel chunk (blockIdx.x).  Each wave stages 32 pixels of dy [32][16]
 // and of every column block's x gather [32][16] in its own LDS region and feeds the
 // MFMA with ds_read_b64_tr_b16 transposed reads (K = pixels).
-typedef short s16x4t __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ bf16x8 tr_frag(const bf16* tile, int lane) {
   // 16x16x32 operand whose K index is the tile row (32 rows x 16 cols, 32-byte rows):
   // lane l gets column (l & 15), rows 8*(l>>4) + 0..7
   const int q = (lane & 15) >> 2, p = lane & 3, g = lane >> 4;
   const bf16* a0 = tile + (8 * g + q) * 16 + 4 * p;
   const bf16* a1 = tile + (8 * g + 4 + q) * 16 + 4 * p;
-  const s16x4t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4t))(a0));
-  const s16x4t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4t))(a1));
-  typedef short s16x8t __attribute__((ext_vector_type(8)));
-  const s16x8t r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, r);
+  return tr_pair(tr_read(a0), tr_read(a1));
 }
 
 constexpr int WG_NCB = 9;   // column blocks per block (3x3 taps of one 16-channel block)
@@ -779,19 +755,9 @@ dw_wgrad_kernel(const bf16* __restrict__ dy, const bf16* __restrict__ x, float* 
 // zeroed), so a thread has ~20 16-byte loads in flight instead of one.
 constexpr int DW_SW = 8;
 
-// n / d for 0 <= n < 2^31 as a multiply-high, an add and a shift, with the divisor's magic
-// number computed on the host: the strip kernels split their item index into (image, row,
-// strip, channel group) once per item, and three 64-bit divisions there cost more
-// instructions than the item's FMAs
-struct FastDiv {
-  unsigned d, m, s;
-  FastDiv() = default;
-  explicit FastDiv(unsigned dv) : d(dv), m(0), s(0) {
-    while ((1u << s) < d) ++s;   // ceil(log2 d)
-    m = (unsigned)((((unsigned long long)1 << 32) * (((unsigned long long)1 << s) - d)) / d + 1);
-  }
-  __device__ __forceinline__ unsigned div(unsigned n) const { return (__umulhi(n, m) + n) >> s; }
-};
+// FastDiv (gfx950.h): the strip kernels split their item index into (image, row, strip,
+// channel group) once per item, and three 64-bit divisions there cost more instructions
+// than the item's FMAs
 // item i = ((n * R + row) * Q + q) * G + cg
 struct Idx3 {
   FastDiv g, q, r;

@@ -23,32 +23,19 @@
 //     slot s ^ mcswz(r); fragments by two ds_read_b64_tr_b16, conflict-free;
 // * the MFMA computes C^T tiles (B fragment as the A operand), so each lane ends with 4
 //   consecutive columns of one output row: 8-byte stores straight from registers.
-#include "common.h"
+#include "gfx950.h"
 #include "convgeom.h"
 
 namespace g256 {
 
 using igemm::ConvGeom;
-using igemm::FastDiv;
 using igemm::NSTAT;
 using igemm::tap_pat;
 using igemm::NO_TAP;
 
 constexpr int BM = 256, BK = 64, NTHR = 512;
-typedef __amdgpu_buffer_rsrc_t Rsrc;
-constexpr unsigned OOB = 0x80000000u;
-
-__device__ __forceinline__ Rsrc rsrc(const void* base) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, 0x7ffffff0, 0x00020000);
-}
-__device__ __forceinline__ void bar() { asm volatile("s_barrier" ::: "memory"); }
-template <int N> __device__ __forceinline__ void vmwait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void dma16(Rsrc rs, char* dst, unsigned voff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)dst, 16, voff, 0, 0, 0);
-}
 
 // --------------------------------------------------------------------- LDS images
-__device__ __forceinline__ int kcswz(int r) { return (r >> 1) & 7; }
 template <int R> __device__ __forceinline__ int mcswz(int r) {
   if constexpr (R == 128) return ((r & 3) | (((r >> 3) & 1) << 2)) << 1;   // 256-B k-rows
   else return (((r >> 1) & 1) | (((r >> 3) & 1) << 1)) << 1;               // 128-B k-rows
@@ -60,7 +47,7 @@ template <int R> struct Img {
   static constexpr int NC = R / 64;
   // KC: copy c of wave w -> image rows (w*NC + c)*8 + lane/8, slot lane%8
   __device__ static int kc_row(int w, int c, int lane) { return (w * NC + c) * 8 + (lane >> 3); }
-  __device__ static int kc_chunk(int w, int c, int lane) { return (lane & 7) ^ kcswz(kc_row(w, c, lane)); }
+  __device__ static int kc_chunk(int w, int c, int lane) { return (lane & 7) ^ kc_swz(kc_row(w, c, lane)); }
   // MC: copy c of wave w -> k-rows (w*NC + c)*(512/R) + lane/(R/8), slot lane%(R/8)
   __device__ static int mc_krow(int w, int c, int lane) { return (w * NC + c) * (512 / R) + lane / (R / 8); }
   __device__ static int mc_col(int w, int c, int lane) {   // first mn column of the 16-B chunk copied
@@ -72,7 +59,9 @@ template <int R> struct Img {
 // v_mfma_f32_16x16x32_bf16 (lane l: row l&15, k = 8(l>>4) + e)
 __device__ __forceinline__ bf16x8 frag_kc(const char* img, int rb, int kk, int lane) {
   const int r = rb + (lane & 15), c = kk * 4 + (lane >> 4);
-  return *reinterpret_cast<const bf16x8*>(img + r * 128 + ((c ^ kcswz(r)) << 4));
+  // the kc_off(r, c) layout, as row pointer + slot: summed into one offset first, the address
+  // math compiles differently and every kernel here takes 1-2 more VGPRs
+  return *reinterpret_cast<const bf16x8*>(img + r * 128 + ((c ^ kc_swz(r)) << 4));
 }
 template <int R>
 __device__ __forceinline__ bf16x8 frag_mc(const char* img, int rb, int kk, int lane) {
@@ -82,11 +71,7 @@ __device__ __forceinline__ bf16x8 frag_mc(const char* img, int rb, int kk, int l
   auto addr = [&](int kr) {
     return img + kr * (2 * R) + ((((col >> 3) ^ mcswz<R>(kr))) << 4) + ((col & 7) << 1);
   };
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(addr(k0)));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(addr(k0 + 4)));
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  const s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, r);
+  return tr_pair(tr_read(addr(k0)), tr_read(addr(k0 + 4)));
 }
 template <class L, int R>
 __device__ __forceinline__ bf16x8 frag(const char* img, int rb, int kk, int lane) {
@@ -419,7 +404,7 @@ gemm_kernel(const LA la, const LB lb, const EPI epi, int M, int N, int K) {
   lb.copy(sb, n0, 1, 0, 0u, imgB(0, 1), tid);
   la.copy(sa, m0, 1, 0, 0u, imgA(0, 1), tid);
   vmwait<C::CA + C::CB>();   // A0, B0 landed (this wave)
-  bar();                     // ... for every wave
+  s_barrier();               // ... for every wave
 
   bf16x8 af[MT][2], bf0[NT][2], bf1[NT][2];
   auto mma = [&](int ha, int hb, bf16x8 (&bfr)[NT][2]) {
@@ -455,22 +440,22 @@ gemm_kernel(const LA la, const LB lb, const EPI epi, int M, int N, int K) {
     la.copy(sa, m0, 0, t + 1, dead, imgA(nb, 0), tid);
     lb.copy(sb, n0, 0, t + 1, dead, imgB(nb, 0), tid);
     vmwait<2 * C::CA + C::CB>();   // B1(t)
-    bar();
+    s_barrier();
     mma(0, 0, bf0);
     // P2: A0 x B1
     rdB(imgB(b, 1), bf1);
     lb.copy(sb, n0, 1, t + 1, dead, imgB(nb, 1), tid);
     vmwait<C::CA + 2 * C::CB>();   // A1(t)
-    bar();
+    s_barrier();
     mma(0, 1, bf1);
     // P3: A1 x B1
     rdA(imgA(b, 1));
     la.copy(sa, m0, 1, t + 1, dead, imgA(nb, 1), tid);
-    bar();
+    s_barrier();
     mma(1, 1, bf1);
     // P4: A1 x B0
     vmwait<C::CA + C::CB>();       // A0(t+1), B0(t+1)
-    bar();
+    s_barrier();
     mma(1, 0, bf0);
   }
   vmwait<0>();   // the (zero-filled) copies issued by the last K-tile

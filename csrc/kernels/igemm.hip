@@ -25,7 +25,7 @@
 // Epilogues: bf16 store through an LDS-staged 16 B/lane write (+ fused per-channel BN
 // sum / sum-of-squares, spread over NSTAT copies to avoid same-address atomic
 // contention), fp32 atomic add (split-K weight gradients), fp32 store (+bias).
-#include "common.h"
+#include "gfx950.h"
 #include "convgeom.h"
 #include <stdlib.h>
 #include <map>
@@ -40,9 +40,7 @@ constexpr int BK = 64, NTHR = 256;
 
 
 // ---------------------------------------------------------------- LDS images
-// KC image: [rows][64 k] bf16, 128 B rows, 16 B chunk c of row r stored at
-// chunk c ^ ((r>>1)&7): the 16-lane groups of ds_read_b128 hit 16 distinct slots.
-__device__ __forceinline__ int kc_off(int r, int c) { return r * 128 + ((c ^ ((r >> 1) & 7)) << 4); }
+// KC image: [rows][64 k] bf16 in the 128-byte-row swizzle of gfx950.h (kc_off).
 // MC image: [64 k][R mn] bf16 (R*2-byte rows); each 32-lane half of a tr_b16 read
 // (4 k-rows x 64 B) covers 16 distinct 16 B slots of the 256 B bank row.
 template <int R>
@@ -70,45 +68,19 @@ __device__ __forceinline__ bf16x8 read_frag(const char* lds, int base, int s, in
     const int col = m0 + 4 * p;
     const int a0 = mc_off<R>(k0 + q, col >> 3) + (col & 7) * 2;
     const int a1 = mc_off<R>(k0 + 4 + q, col >> 3) + (col & 7) * 2;
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(lds + a0));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(lds + a1));
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, r);
+    return tr_pair(tr_read(lds + a0), tr_read(lds + a1));
   }
 }
 
 // ---------------------------------------------------------------- buffer loads
-// Every operand load is a branch-free raw buffer load: the per-thread 32-bit voffset is
-// precomputed (relative to a wave-uniform base that moves per block / K-tile), and a
-// load that must read zero (padding tap, row past M, K tail) gets voffset OOB, past
-// num_records, so the hardware returns 0.  No exec-mask branches around loads means the
-// compiler sees a fixed number of loads per K-tile and can wait with counted vmcnt
-// instead of draining all of them, which is what lets loads stay in flight across the
-// MFMA phase (two tiles deep with PF=2).
-typedef __amdgpu_buffer_rsrc_t Rsrc;
-constexpr unsigned OOB = 0x80000000u;
-__device__ __forceinline__ Rsrc rsrc(const void* base) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, 0x7ffffff0, 0x00020000);
-}
-__device__ __forceinline__ uint4 bload(Rsrc r, unsigned voff) {
-  return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
-}
-// LDS-DMA (buffer_load ... lds): 16 B per lane straight into LDS, lane-linear from the
-// wave-uniform destination `dst` (no VGPR round trip and no ds_write); an OOB voffset
-// writes zeros.  The KC images below are filled this way by the DMA main loop (PF = 3):
-// lane l of wave w, copy i, lands in image row w*8 + (l>>3) + 32i at slot l&7, so the
-// XOR swizzle moves to the source side - the lane fetches logical chunk (l&7) ^ swz(row),
-// and swz(row) = (tid>>4)&7 for every copy i.
-__device__ __forceinline__ void dma16(Rsrc rs, char* dst, unsigned voff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)dst, 16, voff, 0, 0, 0);
-}
-__device__ __forceinline__ int dma_chunk(int tid) { return (tid & 7) ^ ((tid >> 4) & 7); }
+// Operand loads are the branch-free raw buffer loads of gfx950.h (loads stay in flight two
+// tiles deep with PF=2).  The KC images below are filled by LDS-DMA in the DMA main loop
+// (PF = 3): lane l of wave w, copy i, lands in image row w*8 + (l>>3) + 32i at slot l&7, so
+// the XOR swizzle moves to the source side - the lane fetches logical chunk
+// dma_chunk(tid), the same for every copy i.
 __device__ __forceinline__ char* dma_dst(char* img, int tid) {
   return img + __builtin_amdgcn_readfirstlane(tid >> 6) * 1024;
 }
-template <int N> __device__ __forceinline__ void vmwait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 
 // ---------------------------------------------------------------- loaders
@@ -1025,17 +997,17 @@ struct EpiSlabFused {
           if (m < M) part[(size_t)m * ld + n] = acc[i][j][r];
         }
       }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vmwait<0>();
     __syncthreads();
     int* flag = reinterpret_cast<int*>(lds);
     if (tid == 0) {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      vmwait<0>();
       const unsigned t = __hip_atomic_fetch_add(cnt + blockIdx.x, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       const int last = t == gridDim.z - 1;
       if (last) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        vmwait<0>();
         __hip_atomic_store(cnt + blockIdx.x, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       flag[0] = last;

@@ -25,20 +25,13 @@
 //     (R+3)/R times instead of 16 times.
 //   0 (direct): lane (p, h) reads its B-fragment (16 B: channels 8h..8h+7 of s2d pixel
 //     (oh+r, ow+s)) straight from global memory per K-step (r, s), NB-1 tiles prefetched.
-#include "common.h"
+#include "gfx950.h"
 #include <stdlib.h>
 
 namespace {
 
 constexpr int SC_NT = 256;
 constexpr int SC_BAND_BYTES = 48 * 1024;   // one band image buffer (x2 for double-buffering)
-
-__device__ __forceinline__ bf16x8 ldfrag(const bf16* p) { return __builtin_bit_cast(bf16x8, ldg16(p)); }
-
-typedef __amdgpu_buffer_rsrc_t Rsrc;
-__device__ __forceinline__ Rsrc make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, bytes, 0x00020000);
-}
 
 // filter fragments: A[co][k], co = 32b + p, k = 16s + 8h
 __device__ __forceinline__ void load_filter(bf16x8 (&wf)[2][16], const bf16* w, int p, int h) {
@@ -212,11 +205,9 @@ stem_conv_band_kernel(const bf16* __restrict__ x, const bf16* __restrict__ w, bf
     const int n = bb / bpi, oh0 = (bb - n * bpi) * R;
     const int rr = min(R, Ho - oh0);
     const unsigned bytes = (unsigned)(rr + 3) * row_bytes;
-    const Rsrc rs = make_rsrc(reinterpret_cast<const char*>(x) + ((long)n * Hb + oh0) * row_bytes, bytes);
+    const Rsrc rs = rsrc(reinterpret_cast<const char*>(x) + ((long)n * Hb + oh0) * row_bytes, bytes);
     char* dst = img + __builtin_amdgcn_readfirstlane(wave) * 1024;
-    for (unsigned off = 0; off < bytes; off += SC_NT * 16)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(dst + off), 16,
-                                               off + tid * 16, 0, 0, 0);
+    for (unsigned off = 0; off < bytes; off += SC_NT * 16) dma16(rs, dst + off, off + tid * 16);
   };
 
   bf16x8 wf[2][16];
@@ -227,13 +218,13 @@ stem_conv_band_kernel(const bf16* __restrict__ x, const bf16* __restrict__ w, bf
   auto band = [&](int bb, const char* img, char* nimg) {
     // this thread's DMA of band bb landed; the tile stores issued after it may stay in
     // flight (a full band: 7 tiles x 4 stores per wave)
-    if (stores >= 28) asm volatile("s_waitcnt vmcnt(28)" ::: "memory");
-    else if (stores >= 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else if (stores >= 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (stores >= 28) vmwait<28>();
+    else if (stores >= 16) vmwait<16>();
+    else if (stores >= 8) vmwait<8>();
+    else vmwait<0>();
     // ... everyone's, and the previous band read by all (a bare barrier: __syncthreads'
     // release fence would also drain the stores)
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    lds_barrier();
     stores = 0;
     if (bb + 1 < b1) fetch(bb + 1, nimg);
     const int n = bb / bpi, oh0 = (bb - n * bpi) * R;

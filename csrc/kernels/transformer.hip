@@ -14,7 +14,7 @@
 // Dropout masks are a counter-based hash of (seed, site salt, element index): nothing is
 // stored, backward regenerates the mask, and the seed lives in device memory so a
 // captured HIP graph advances it on every replay.
-#include "common.h"
+#include "gfx950.h"
 #include "dropout.h"
 #include <type_traits>
 
@@ -516,11 +516,7 @@ __device__ __forceinline__ bf16x8 tr_frag(const char* lds, int base, int k0, int
   const int kr = k0 + 8 * (g >> 1);
   const int a0 = img_off<W>(kr + q, col >> 3) + (col & 7) * 2;
   const int a1 = img_off<W>(kr + 4 + q, col >> 3) + (col & 7) * 2;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(lds + a0));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(lds + a1));
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  const s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, r);
+  return tr_pair(tr_read(lds + a0), tr_read(lds + a1));
 }
 // K-contiguous fragment of row `row` straight from global (ld elements per row)
 __device__ __forceinline__ bf16x8 g_frag(const bf16* base, int ld, int row, int s, int lane) {
