@@ -37,6 +37,10 @@ static __device__ __forceinline__ Rsrc rsrc(const void* base, unsigned bytes) {
 static __device__ __forceinline__ uint4 bload(Rsrc r, unsigned voff) {
   return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
 }
+// the same with a compile-time byte offset in the instruction (as bstore's `imm`)
+static __device__ __forceinline__ uint4 bload(Rsrc r, unsigned voff, int imm) {
+  return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, voff + imm, 0, 0));
+}
 // branch-free 16-byte store, dropped for an out-of-range voffset
 static __device__ __forceinline__ void bstore(Rsrc r, unsigned voff, int imm, const uint4& v) {
   typedef unsigned u32x4 __attribute__((ext_vector_type(4)));

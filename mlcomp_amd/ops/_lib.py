@@ -97,6 +97,8 @@ _SIGS = {
     'mlc_conv1x1_fwd': [vp] * 5 + [i64, i32, i32, vp],
     'mlc_conv1x1_fwd_ok': [i32, i32],
     'mlc_conv1x1_fwd_get_set': [i32, i32],
+    'mlc_conv1x1_fwd_res': [vp] * 4 + [i32, vp, i32, i64, i32, i32, vp],
+    'mlc_conv1x1_fwd_res_ok': [i32, i32],
     'mlc_maxpool_fwd': [vp, vp, vp] + [i32] * 9 + [vp],
     'mlc_maxpool_bwd': [vp, vp, vp] + [i32] * 9 + [vp],
     'mlc_stem_pool_fwd': [vp] * 6 + [i32] * 4 + [vp],

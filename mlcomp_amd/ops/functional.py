@@ -118,6 +118,68 @@ def conv1x1_fwd(x: torch.Tensor, w: torch.Tensor, stats: Tuple[torch.Tensor, tor
     return y
 
 
+# Inference form of the streaming kernel (conv1x1_fwd_res): a BN-folded channel-expanding 1x1
+# unit, z equal to conv2d_fwd_res's element for element.  MLC_CONV1X1_RES=0 keeps the igemm path;
+# a unit takes the streaming kernel from CONV1X1_RES_MIN_ROWS[(Cin, Cout)] rows on (a pair
+# without an entry is never dispatched), MLC_CONV1X1_RES_MIN_ROWS=<n> overrides the threshold
+# of every pair.  The defaults are the smallest row counts measured, those of batch 32, where the
+# kernel already wins by more than three igemm spreads (profiles/conv1x1_res/shapes.jsonl, us per
+# call, streaming median against igemm minimum): (128, 512) 16.9 against 22.7 at 25,088 rows;
+# (256, 1024) 13.8 against 15.3 at 6,272 rows.  Fewer rows were not measured and stay on igemm.
+CONV1X1_RES = os.environ.get('MLC_CONV1X1_RES', '1') == '1'
+CONV1X1_RES_MIN_ROWS_DEFAULT = {(128, 512): 25088, (256, 1024): 6272}
+CONV1X1_RES_MIN_ROWS = (int(os.environ['MLC_CONV1X1_RES_MIN_ROWS'])
+                        if os.environ.get('MLC_CONV1X1_RES_MIN_ROWS') else None)
+
+
+def conv1x1_res_min_rows(Cin, Cout):
+    """Row count from which on ``ConvBN`` dispatches a deploy-mode (Cin, Cout) unit to
+    :func:`conv1x1_fwd_res`; None: never."""
+    if CONV1X1_RES_MIN_ROWS is not None:
+        return CONV1X1_RES_MIN_ROWS
+    return CONV1X1_RES_MIN_ROWS_DEFAULT.get((Cin, Cout))
+
+
+def conv1x1_fwd_res_available(Cin, Cout) -> bool:
+    """True when the inference form of the streaming kernel has an instantiation for
+    (Cin, Cout).  Nothing in it is unordered, so deterministic mode does not matter."""
+    return bool(_lib.load().mlc_conv1x1_fwd_res_ok(Cin, Cout))
+
+
+def conv1x1_fwd_res(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                    addend: Optional[torch.Tensor] = None, act: int = 0,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """z = act(conv1x1(x, w) + bias + addend), exactly as :func:`conv2d_fwd_res` with stride 1
+    and pad 0; GPU tensors run the streaming kernel (a shape without an instantiation raises)."""
+    Co, KH, KW, Ci = w.shape
+    assert (KH, KW) == (1, 1) and x.shape[-1] == Ci, (w.shape, x.shape)
+    assert act in (0, 3), act
+    if addend is not None:
+        assert tuple(addend.shape) == (*x.shape[:-1], Co) and addend.dtype == torch.bfloat16, \
+            (addend.shape, addend.dtype)
+    if not _cuda(x):
+        z = conv2d_fwd_res(x, w, bias, addend, act)
+        if out is not None:
+            out.copy_(z)
+            return out
+        return z
+    assert x.dtype == torch.bfloat16 and x.is_contiguous(), (x.dtype, x.stride())
+    assert w.dtype == torch.bfloat16 and w.is_contiguous() and w.device == x.device, (w.dtype, w.stride(), w.device)
+    assert bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.device == x.device
+                            and bias.numel() == Co), (bias.dtype, bias.shape, bias.device)
+    assert addend is None or addend.device == x.device, addend.device
+    lda = 0
+    if addend is not None:
+        lda = rows_ld(addend)
+        assert lda is not None and lda % 8 == 0 and addend.data_ptr() % 16 == 0, (addend.shape, addend.stride())
+    y = out if out is not None else torch.empty(*x.shape[:-1], Co, device=x.device, dtype=torch.bfloat16)
+    assert y.dtype == torch.bfloat16 and y.is_contiguous() and y.device == x.device \
+        and tuple(y.shape) == (*x.shape[:-1], Co), (y.dtype, y.shape, y.stride(), y.device)
+    _lib.call('mlc_conv1x1_fwd_res', _lib.ptr(x), _lib.ptr(w), _lib.ptr(y), _lib.ptr(bias), int(act),
+              _lib.ptr(addend), lda, x.numel() // Ci, Ci, Co, _lib.stream())
+    return y
+
+
 def conv_transpose2d_fwd(x: torch.Tensor, w: torch.Tensor, out_hw, stride=2, pad=1, dil=1,
                          stats: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
     """y = conv_transpose(x, w) in NHWC, no bias: x [N, Hi, Wi, Cin], w [Cin, KH, KW, Cout]

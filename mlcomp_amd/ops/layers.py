@@ -15,6 +15,7 @@ memset at the start of the step.
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import List, Optional
 
@@ -291,7 +292,10 @@ class ConvBN:
             if self._fold is None:
                 self.refold()
             w_fold, b_fold = self._fold
-            z = Fn.conv2d_fwd_res(x, w_fold, b_fold, res, 3 if self.act else 0, self.stride, self.pad, self.dil)
+            if self._conv1x1_res_ok(x):
+                z = Fn.conv1x1_fwd_res(x, w_fold, b_fold, res, 3 if self.act else 0)
+            else:
+                z = Fn.conv2d_fwd_res(x, w_fold, b_fold, res, 3 if self.act else 0, self.stride, self.pad, self.dil)
             return z, (x, None, z)
         if not self.ctx.training:  # inference BN: running statistics, no stat epilogue
             y = self._conv(x, None, in_affine)
@@ -355,6 +359,20 @@ class ConvBN:
         if self.k != (1, 1) or self.stride != 1 or self.pad != 0 or x.shape[-1] != self.cin_p:
             return False
         return Fn.conv1x1_fwd_available(self.cin_p, self.Co)
+
+    def _conv1x1_res_ok(self, x) -> bool:
+        """The deploy-mode unit can run as the streaming kernel's inference form
+        (MLC_CONV1X1_RES, default on): a plain 1x1 / stride-1 / pad-0 conv on the GPU with at
+        least the pair's threshold of rows (Fn.conv1x1_res_min_rows) whose (Cin, Cout) has an
+        instantiation."""
+        if not (Fn.CONV1X1_RES and x.is_cuda and type(self) is ConvBN and not self.s2d):
+            return False
+        if self.k != (1, 1) or self.stride != 1 or self.pad != 0 or x.shape[-1] != self.cin_p:
+            return False
+        min_rows = Fn.conv1x1_res_min_rows(self.cin_p, self.Co)
+        if min_rows is None or math.prod(x.shape[:-1]) < min_rows:
+            return False
+        return Fn.conv1x1_fwd_res_available(self.cin_p, self.Co)
 
     def _dgrad(self, dy, x_shape, addend=None, out=None, bn=None):
         wt = None
