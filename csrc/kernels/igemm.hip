@@ -598,6 +598,29 @@ struct ClassRows {  // dgrad class row (n, i, j) -> NHWC pixel (n, i*S+ph, j*S+p
     return ((size_t)n * H + i * c.S + c.ph) * W + j * c.S + c.pw;
   }
 };
+// A row map that also places EpiBF16's compact strided addend: the rows go where `rows`
+// sends them, and the addend is [N, Ho, Wo, ld] with Ho = (H-1)/S + 1, Wo = (W-1)/S + 1,
+// its pixel (n, i, j) lying under output pixel (n, i*S, j*S).  That is the input gradient
+// of a 1x1 / stride-S / pad-0 conv without its structural zeros: the epilogue loads a
+// chunk only under the pixels that have one.  A type of its own, so the launches with the
+// same-layout addend (or none) keep their code.
+template <class Rows = IdentityRows>
+struct StridedAddRows {
+  Rows rows; int Ho, Wo; FastDiv fW, fH, fS;
+  __device__ __forceinline__ size_t operator()(int m) const { return rows(m); }
+  // output pixel -> its addend pixel; false: none (h or w is no multiple of S)
+  __device__ __forceinline__ bool addend_pixel(size_t pix, size_t& cpix) const {
+    unsigned t, n, h, w, hq, hr, wq, wr;
+    fW.divmod((unsigned)pix, t, w);
+    fH.divmod(t, n, h);
+    fS.divmod(h, hq, hr);
+    fS.divmod(w, wq, wr);
+    cpix = ((size_t)n * Ho + hq) * Wo + wq;
+    return (hr | wr) == 0;
+  }
+};
+template <class R> struct HasStridedAdd { static constexpr bool value = false; };
+template <class R> struct HasStridedAdd<StridedAddRows<R>> { static constexpr bool value = true; };
 
 // BatchNorm-backward reduction fused into the epilogue of the dgrad that produces the
 // final gradient dU of a BN's output (the branch-point sum is already in via addend):
@@ -686,6 +709,8 @@ __device__ __forceinline__ void dense_dact8(float (&a)[8], int act, uint4 zv) {
 
 template <class RowMap = IdentityRows, bool kDense = false>
 struct EpiBF16 {  // bf16 [M][ld] store (+ addend), optional per-column sum / sum of squares
+  // addend: laid out as out (and free to alias it), or, under a StridedAddRows row map, the
+  // compact [N, Ho, Wo, ld] tensor that map places
   bf16* out; int ld; float* sum; float* sumsq; RowMap rowmap; const bf16* addend = nullptr;
   BnBwdEpi bn = {};
   // dense-layer extras: out = act(acc + bias) (pre-activation, or with act 2 the
@@ -784,13 +809,15 @@ struct EpiBF16 {  // bf16 [M][ld] store (+ addend), optional per-column sum / su
     constexpr int UMAX = kDense ? 4 : 8;   // conv epilogues: every row's loads in flight at once
     constexpr int U = ITERS < UMAX ? ITERS : UMAX;
     const bool has_add = addend != nullptr, has_mask = red && bn.mask, has_y1 = red && bn.y1;
+    // the addend's form is the row map's type: same layout as out, or compact strided
+    constexpr bool kSAdd = HasStridedAdd<RowMap>::value;
 #pragma unroll 1
     for (int it0 = 0; it0 < ITERS; it0 += U) {
       constexpr int UB = kDense ? 1 : U;   // BN-reduction operands (conv dgrad only)
       constexpr int UD = kDense ? U : 1;   // activation-derivative operand (dense only)
       uint4 vv[U], aa[U], zz[UB], p0[UB], p1[UB], du[UD];
       size_t off[U];
-      bool ok[U];
+      bool ok[U], hit[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         int row = tid / CPR + RPI * (it0 + u);
@@ -798,11 +825,20 @@ struct EpiBF16 {  // bf16 [M][ld] store (+ addend), optional per-column sum / su
         if (!rin) row = 0;                          // idle thread / past the tile: read row 0, no store
         const int m = m0 + row;
         ok[u] = rin && m < M && nc < N;
-        off[u] = ok[u] ? rowmap(m) * ld + nc : 0;   // rows/cols outside: element 0 (valid)
+        const size_t pix = ok[u] ? rowmap(m) : 0;
+        off[u] = ok[u] ? pix * ld + nc : 0;         // rows/cols outside: element 0 (valid)
         vv[u] = *reinterpret_cast<const uint4*>(lds + row * RS + c * 16);
         const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
-        // unconditional per lane (the store is what ok[u] guards), uniform per pointer
-        aa[u] = has_add ? ldg16(addend + off[u]) : zero;
+        if constexpr (kSAdd) {
+          // per lane: only a stored chunk whose pixel lies on the stride grid has an addend
+          size_t cpix = 0;
+          hit[u] = has_add && ok[u] && rowmap.addend_pixel(pix, cpix);
+          aa[u] = hit[u] ? ldg16(addend + cpix * ld + nc) : zero;
+        } else {
+          // unconditional per lane (the store is what ok[u] guards), uniform per pointer
+          hit[u] = has_add;
+          aa[u] = has_add ? ldg16(addend + off[u]) : zero;
+        }
         if constexpr (!kDense) {
           zz[u] = has_mask ? ldg16(bn.mask + off[u]) : zero;
           p0[u] = red ? ldg16(bn.y0 + off[u]) : zero;
@@ -825,7 +861,7 @@ struct EpiBF16 {  // bf16 [M][ld] store (+ addend), optional per-column sum / su
           dense_act8(a, act, preact ? preact + off[u] : nullptr);
           if (dact) dense_dact8(a, act, du[u]);
           }
-          if (has_add) {  // fused residual-gradient sum (dx of a branch point)
+          if (hit[u]) {   // fused residual-gradient sum (dx of a branch point)
             float b[8];
             unpack8(aa[u], b);
 #pragma unroll
@@ -1937,21 +1973,49 @@ MLC_EXPORT int mlc_conv_fwd_ld(const bf16* x, const bf16* w, bf16* y, int ldy, i
                        nullptr, st);
 }
 
+// The addend of a dgrad entry in either of EpiBF16's forms: `same` has dx's layout (and may
+// alias dx); `compact` is [N, (H-1)/S + 1, (W-1)/S + 1, C], added at the pixels whose h and w
+// are multiples of S (StridedAddRows).  At most one of them.
+struct DgradAddend {
+  const bf16* same = nullptr; const bf16* compact = nullptr; int S = 1;
+};
+
 // Argument checks of the dgrad entries (0: fine); bn holds the fused BN-backward operands.
-static int dgrad_check(const BnBwdEpi& bn, int N, int H, int W, int C, int Co, int KH, int KW, int stride,
-                       const float* sum, const float* sumsq) {
+// The compact addend's rows are dx's (C elements), so C % 8 covers its 16-byte chunks too.
+static int dgrad_check(const BnBwdEpi& bn, const DgradAddend& add, int N, int H, int W, int C, int Co, int KH,
+                       int KW, int stride, const float* sum, const float* sumsq) {
   if (C % 8 || Co % 8 || KH > 15 || KW > 16 || stride < 1 || ((sum == nullptr) != (sumsq == nullptr))) return -1;
+  if (add.S < 1 || (add.compact && add.same)) return -1;
   if (bn.y0 && g_mlc_det && ((long)N * H * W + 63) / 64 > g_mlc_ncopy) return -2;
   if (bn.msc0 && (!bn.msh0 || !bn.y0 || (bn.msc1 && (!bn.msh1 || !bn.y1)))) return -1;
   if (bn.y0 && (!bn.mean0 || !bn.sums0 || (bn.y1 && (!bn.mean1 || !bn.sums1)))) return -1;
   return 0;
 }
 
+// One dgrad GEMM: EpiBF16 over `rows` with the addend in either form (H, W: dx's), on the
+// tile pick_tile gives.
+template <class Rows, class FA, class FB>
+static hipError_t launch_dgrad(const Rows& rows, bf16* dx, const DgradAddend& add, const BnBwdEpi& bn, float* sum,
+                               float* sumsq, int H, int W, int M, int C, int K, hipStream_t st, const FA& fa,
+                               const FB& fb) {
+  const int tile = pick_tile(M, C);
+  if (add.compact) {
+    const StridedAddRows<Rows> srows{rows, (H - 1) / add.S + 1, (W - 1) / add.S + 1, FastDiv(W), FastDiv(H),
+                                     FastDiv(add.S)};
+    EpiBF16<StridedAddRows<Rows>> epi{dx, C, sum, sumsq, srows, add.compact, bn};
+    epi.ncopy = g_mlc_ncopy;
+    return launch_tiles(tile, M, C, K, 1, st, epi, fa, fb);
+  }
+  EpiBF16<Rows> epi{dx, C, sum, sumsq, rows, add.same, bn};
+  epi.ncopy = g_mlc_ncopy;
+  return launch_tiles(tile, M, C, K, 1, st, epi, fa, fb);
+}
+
 // The general dgrad: one GEMM per stride-parity class of dx (see conv_dgrad_impl).  MkB is
 // the filter's loader factory: MkConvDgradB for w[Co][KH][KW][C], MkConvDgradBT for the
 // transposed, flipped wt[C][KH][KW][Co].  pad is the exports' (possibly packed) value.
 template <class MkB>
-static int dgrad_classes(const bf16* dy, const bf16* w, bf16* dx, const bf16* addend, const BnBwdEpi& bn,
+static int dgrad_classes(const bf16* dy, const bf16* w, bf16* dx, const DgradAddend& add, const BnBwdEpi& bn,
                          const ConvGeom& g, int pad, float* sum, float* sumsq, hipStream_t st) {
   hipError_t err = hipSuccess;
   // the parity-class GEMMs run one after another on the stream, so in deterministic mode
@@ -1963,25 +2027,20 @@ static int dgrad_classes(const bf16* dy, const bf16* w, bf16* dx, const bf16* ad
       const int M = g.N * cl.Hc * cl.Wc, K = cl.nr * cl.ns * cl.ncb * BK;
       if (M <= 0) continue;
       if (sum && g_mlc_det && (M + 63) / 64 > g_mlc_ncopy) return -2;
-      const int tile = pick_tile(M, g.C);
       const MkConvDgradA fa{dy, g, M, K, cl};
       const MkB fb{w, g, cl};
-      if (g.stride == 1) {
-        EpiBF16<> epi{dx, g.C, sum, sumsq, IdentityRows{}, addend, bn};
-        epi.ncopy = g_mlc_ncopy;
-        err = launch_tiles(tile, M, g.C, K, 1, st, epi, fa, fb);
-      } else {
-        EpiBF16<ClassRows> epi{dx, g.C, sum, sumsq, ClassRows{cl, g.H, g.W}, addend, bn};
-        epi.ncopy = g_mlc_ncopy;
-        err = launch_tiles(tile, M, g.C, K, 1, st, epi, fa, fb);
-      }
+      if (g.stride == 1)
+        err = launch_dgrad(IdentityRows{}, dx, add, bn, sum, sumsq, g.H, g.W, M, g.C, K, st, fa, fb);
+      else
+        err = launch_dgrad(ClassRows{cl, g.H, g.W}, dx, add, bn, sum, sumsq, g.H, g.W, M, g.C, K, st, fa, fb);
       if (err != hipSuccess) return err;
     }
   return err;
 }
 
-// dx[N,H,W,C] = conv_transpose(dy[N,Ho,Wo,Co], w) (+ addend, same layout as dx; may
-// alias dx) -- the addend fuses the gradient sum at a residual branch point.
+// dx[N,H,W,C] = conv_transpose(dy[N,Ho,Wo,Co], w) (+ addend, same layout as dx and free
+// to alias it, or compact strided: DgradAddend) -- the addend fuses the gradient sum at a
+// residual branch point.
 // bn_y0 != null additionally fuses the backward reduction of the BatchNorm(s) whose
 // output gradient dx is (see BnBwdEpi): dx is stored masked by bn_mask > 0 (or by the
 // mask recomputed from bn_y0/bn_y1 with bn_msc/bn_msh) and the partial sums go to
@@ -1991,7 +2050,7 @@ static int dgrad_classes(const bf16* dy, const bf16* w, bf16* dx, const bf16* ad
 // is written by a GEMM epilogue and no structurally-zero products are computed.
 // sum/sumsq (optional): per-column BN forward statistics of dx, as in mlc_conv_fwd - the
 // transposed-conv forward (mlc_conv_tr_fwd) is this GEMM with a BatchNorm after it.
-static int conv_dgrad_impl(const bf16* dy, const bf16* w, bf16* dx, const bf16* addend, int N,
+static int conv_dgrad_impl(const bf16* dy, const bf16* w, bf16* dx, const DgradAddend& add, int N,
                            int H, int W, int C, int Co, int KH, int KW, int stride, int pad,
                            int dil, int Ho, int Wo, const bf16* bn_mask, const bf16* bn_y0,
                            const float* bn_mean0, float* bn_sums0, const bf16* bn_y1,
@@ -2000,17 +2059,16 @@ static int conv_dgrad_impl(const bf16* dy, const bf16* w, bf16* dx, const bf16* 
                            float* sum, float* sumsq, hipStream_t st) {
   const BnBwdEpi bn{bn_mask, bn_y0, bn_mean0, bn_sums0, bn_y1, bn_mean1, bn_sums1,
                     bn_msc0, bn_msh0, bn_msc1, bn_msh1, g_mlc_ncopy};
-  if (const int rc = dgrad_check(bn, N, H, W, C, Co, KH, KW, stride, sum, sumsq)) return rc;
+  if (const int rc = dgrad_check(bn, add, N, H, W, C, Co, KH, KW, stride, sum, sumsq)) return rc;
   const ConvGeom g = mkgeom(N, H, W, C, Co, KH, KW, stride, pad, dil, Ho, Wo);
   if (KH == 1 && KW == 1 && stride == 1 && pad == 0) {
     const DgradClass cl = mkclass(1, 0, 0, H, W, Ho, Wo, Co, 1, 1, 0, dil);
     const int M = N * H * W, K = cl.ncb * BK;
     if (sum && g_mlc_det && (M + 63) / 64 > g_mlc_ncopy) return -2;
-    EpiBF16<> epi{dx, C, sum, sumsq, IdentityRows{}, addend, bn};
-    epi.ncopy = g_mlc_ncopy;
-    return launch_tiles(pick_tile(M, C), M, C, K, 1, st, epi, MkMatKC{dy, Co, M, Co}, MkConvDgradB{w, g, cl});
+    return launch_dgrad(IdentityRows{}, dx, add, bn, sum, sumsq, H, W, M, C, K, st, MkMatKC{dy, Co, M, Co},
+                        MkConvDgradB{w, g, cl});
   }
-  return dgrad_classes<MkConvDgradB>(dy, w, dx, addend, bn, g, pad, sum, sumsq, st);
+  return dgrad_classes<MkConvDgradB>(dy, w, dx, add, bn, g, pad, sum, sumsq, st);
 }
 
 MLC_EXPORT int mlc_conv_dgrad(const bf16* dy, const bf16* w, bf16* dx, const bf16* addend, int N,
@@ -2020,9 +2078,26 @@ MLC_EXPORT int mlc_conv_dgrad(const bf16* dy, const bf16* w, bf16* dx, const bf1
                               const float* bn_mean1, float* bn_sums1, const float* bn_msc0,
                               const float* bn_msh0, const float* bn_msc1, const float* bn_msh1,
                               hipStream_t st) {
-  return conv_dgrad_impl(dy, w, dx, addend, N, H, W, C, Co, KH, KW, stride, pad, dil, Ho, Wo, bn_mask, bn_y0,
-                         bn_mean0, bn_sums0, bn_y1, bn_mean1, bn_sums1, bn_msc0, bn_msh0, bn_msc1, bn_msh1,
+  return conv_dgrad_impl(dy, w, dx, DgradAddend{addend}, N, H, W, C, Co, KH, KW, stride, pad, dil, Ho, Wo, bn_mask,
+                         bn_y0, bn_mean0, bn_sums0, bn_y1, bn_mean1, bn_sums1, bn_msc0, bn_msh0, bn_msc1, bn_msh1,
                          nullptr, nullptr, st);
+}
+
+// mlc_conv_dgrad with the addend in its compact strided form: sadd is
+// [N, (H-1)/sadd_stride + 1, (W-1)/sadd_stride + 1, C], added at the dx pixels whose h and w
+// are multiples of sadd_stride (the input gradient of a 1x1 / strided / pad-0 shortcut conv,
+// never expanded to dx's resolution).  dx must not alias it.  -1 for sadd_stride < 1 or
+// both addends.
+MLC_EXPORT int mlc_conv_dgrad_sadd(const bf16* dy, const bf16* w, bf16* dx, const bf16* addend, const bf16* sadd,
+                                   int sadd_stride, int N, int H, int W, int C, int Co, int KH, int KW,
+                                   int stride, int pad, int dil, int Ho, int Wo, const bf16* bn_mask,
+                                   const bf16* bn_y0, const float* bn_mean0, float* bn_sums0, const bf16* bn_y1,
+                                   const float* bn_mean1, float* bn_sums1, const float* bn_msc0,
+                                   const float* bn_msh0, const float* bn_msc1, const float* bn_msh1,
+                                   hipStream_t st) {
+  return conv_dgrad_impl(dy, w, dx, DgradAddend{addend, sadd, sadd_stride}, N, H, W, C, Co, KH, KW, stride, pad, dil,
+                         Ho, Wo, bn_mask, bn_y0, bn_mean0, bn_sums0, bn_y1, bn_mean1, bn_sums1, bn_msc0, bn_msh0,
+                         bn_msc1, bn_msh1, nullptr, nullptr, st);
 }
 
 // Transposed convolution (nn.ConvTranspose2d, no bias): y[N, Ho, Wo, Cout] from
@@ -2040,7 +2115,7 @@ MLC_EXPORT int mlc_conv_tr_fwd(const bf16* x, const bf16* w, bf16* y, float* sum
   unpack_pad(pad, pad_h, pad_w);
   if (Hi != (Ho + 2 * pad_h - dil * (KH - 1) - 1) / stride + 1 || Wi != (Wo + 2 * pad_w - dil * (KW - 1) - 1) / stride + 1)
     return -1;
-  return conv_dgrad_impl(x, w, y, nullptr, N, Ho, Wo, Cout, Cin, KH, KW, stride, pad, dil, Hi, Wi, nullptr,
+  return conv_dgrad_impl(x, w, y, DgradAddend{}, N, Ho, Wo, Cout, Cin, KH, KW, stride, pad, dil, Hi, Wi, nullptr,
                          nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                          nullptr, sum, sumsq, st);
 }
@@ -2051,6 +2126,35 @@ MLC_EXPORT int mlc_conv_tr_fwd(const bf16* x, const bf16* w, bf16* y, float* sum
 // LDS reads.  A stride-1 conv's dgrad IS a forward conv of dy over wt with pad' =
 // dil*(K-1) - pad, so it runs on the forward loaders; strided convs keep the parity-class
 // GEMMs with the ConvDgradBT filter loader.
+static int conv_dgrad_t_impl(const bf16* dy, const bf16* wt, bf16* dx, const DgradAddend& add, int N,
+                             int H, int W, int C, int Co, int KH, int KW, int stride, int pad,
+                             int dil, int Ho, int Wo, const bf16* bn_mask, const bf16* bn_y0,
+                             const float* bn_mean0, float* bn_sums0, const bf16* bn_y1,
+                             const float* bn_mean1, float* bn_sums1, const float* bn_msc0,
+                             const float* bn_msh0, const float* bn_msc1, const float* bn_msh1,
+                             hipStream_t st) {
+  const BnBwdEpi bn{bn_mask, bn_y0, bn_mean0, bn_sums0, bn_y1, bn_mean1, bn_sums1,
+                    bn_msc0, bn_msh0, bn_msc1, bn_msh1, g_mlc_ncopy};
+  if (const int rc = dgrad_check(bn, add, N, H, W, C, Co, KH, KW, stride, nullptr, nullptr)) return rc;
+  int pad_h, pad_w;
+  unpack_pad(pad, pad_h, pad_w);
+  const int ph = dil * (KH - 1) - pad_h, pw = dil * (KW - 1) - pad_w;
+  if (stride == 1 && ph >= 0 && pw >= 0) {
+    if (Ho != H + 2 * pad_h - dil * (KH - 1) || Wo != W + 2 * pad_w - dil * (KW - 1)) return -1;
+    const int M = N * H * W, K = KH * KW * Co;
+    const MkMatKC fb{wt, K, C, K};
+    if (KH == 1 && KW == 1)
+      return launch_dgrad(IdentityRows{}, dx, add, bn, nullptr, nullptr, H, W, M, C, K, st, MkMatKC{dy, Co, M, Co},
+                          fb);
+    // geometry of the equivalent forward conv: input dy [N, Ho, Wo, Co], output [N, H, W, C]
+    const ConvGeom gf = mkgeom(N, Ho, Wo, Co, C, KH, KW, 1, pack_pad(ph, pw), dil, H, W);
+    return launch_dgrad(IdentityRows{}, dx, add, bn, nullptr, nullptr, H, W, M, C, K, st, MkConvFwdA{dy, gf, M, K},
+                        fb);
+  }
+  const ConvGeom g = mkgeom(N, H, W, C, Co, KH, KW, stride, pad, dil, Ho, Wo);
+  return dgrad_classes<MkConvDgradBT>(dy, wt, dx, add, bn, g, pad, nullptr, nullptr, st);
+}
+
 MLC_EXPORT int mlc_conv_dgrad_t(const bf16* dy, const bf16* wt, bf16* dx, const bf16* addend, int N,
                                 int H, int W, int C, int Co, int KH, int KW, int stride, int pad,
                                 int dil, int Ho, int Wo, const bf16* bn_mask, const bf16* bn_y0,
@@ -2058,25 +2162,22 @@ MLC_EXPORT int mlc_conv_dgrad_t(const bf16* dy, const bf16* wt, bf16* dx, const 
                                 const float* bn_mean1, float* bn_sums1, const float* bn_msc0,
                                 const float* bn_msh0, const float* bn_msc1, const float* bn_msh1,
                                 hipStream_t st) {
-  const BnBwdEpi bn{bn_mask, bn_y0, bn_mean0, bn_sums0, bn_y1, bn_mean1, bn_sums1,
-                    bn_msc0, bn_msh0, bn_msc1, bn_msh1, g_mlc_ncopy};
-  if (const int rc = dgrad_check(bn, N, H, W, C, Co, KH, KW, stride, nullptr, nullptr)) return rc;
-  int pad_h, pad_w;
-  unpack_pad(pad, pad_h, pad_w);
-  const int ph = dil * (KH - 1) - pad_h, pw = dil * (KW - 1) - pad_w;
-  if (stride == 1 && ph >= 0 && pw >= 0) {
-    if (Ho != H + 2 * pad_h - dil * (KH - 1) || Wo != W + 2 * pad_w - dil * (KW - 1)) return -1;
-    const int M = N * H * W, K = KH * KW * Co;
-    const int tile = pick_tile(M, C);
-    EpiBF16<> epi{dx, C, nullptr, nullptr, IdentityRows{}, addend, bn};
-    const MkMatKC fb{wt, K, C, K};
-    if (KH == 1 && KW == 1) return launch_tiles(tile, M, C, K, 1, st, epi, MkMatKC{dy, Co, M, Co}, fb);
-    // geometry of the equivalent forward conv: input dy [N, Ho, Wo, Co], output [N, H, W, C]
-    const ConvGeom gf = mkgeom(N, Ho, Wo, Co, C, KH, KW, 1, pack_pad(ph, pw), dil, H, W);
-    return launch_tiles(tile, M, C, K, 1, st, epi, MkConvFwdA{dy, gf, M, K}, fb);
-  }
-  const ConvGeom g = mkgeom(N, H, W, C, Co, KH, KW, stride, pad, dil, Ho, Wo);
-  return dgrad_classes<MkConvDgradBT>(dy, wt, dx, addend, bn, g, pad, nullptr, nullptr, st);
+  return conv_dgrad_t_impl(dy, wt, dx, DgradAddend{addend}, N, H, W, C, Co, KH, KW, stride, pad, dil, Ho, Wo,
+                           bn_mask, bn_y0, bn_mean0, bn_sums0, bn_y1, bn_mean1, bn_sums1, bn_msc0, bn_msh0, bn_msc1,
+                           bn_msh1, st);
+}
+
+// mlc_conv_dgrad_t with the compact strided addend of mlc_conv_dgrad_sadd.
+MLC_EXPORT int mlc_conv_dgrad_t_sadd(const bf16* dy, const bf16* wt, bf16* dx, const bf16* addend, const bf16* sadd,
+                                     int sadd_stride, int N, int H, int W, int C, int Co, int KH, int KW,
+                                     int stride, int pad, int dil, int Ho, int Wo, const bf16* bn_mask,
+                                     const bf16* bn_y0, const float* bn_mean0, float* bn_sums0, const bf16* bn_y1,
+                                     const float* bn_mean1, float* bn_sums1, const float* bn_msc0,
+                                     const float* bn_msh0, const float* bn_msc1, const float* bn_msh1,
+                                     hipStream_t st) {
+  return conv_dgrad_t_impl(dy, wt, dx, DgradAddend{addend, sadd, sadd_stride}, N, H, W, C, Co, KH, KW, stride, pad,
+                           dil, Ho, Wo, bn_mask, bn_y0, bn_mean0, bn_sums0, bn_y1, bn_mean1, bn_sums1, bn_msc0,
+                           bn_msh0, bn_msc1, bn_msh1, st);
 }
 
 namespace {

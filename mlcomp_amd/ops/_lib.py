@@ -33,6 +33,8 @@ _SIGS = {
     'mlc_conv_fwd_ld': [vp, vp, vp] + [i32] * 13 + [vp],
     'mlc_conv_dgrad': [vp] * 4 + [i32] * 12 + [vp] * 11 + [vp],
     'mlc_conv_dgrad_t': [vp] * 4 + [i32] * 12 + [vp] * 11 + [vp],
+    'mlc_conv_dgrad_sadd': [vp] * 5 + [i32] * 13 + [vp] * 11 + [vp],
+    'mlc_conv_dgrad_t_sadd': [vp] * 5 + [i32] * 13 + [vp] * 11 + [vp],
     'mlc_bilinear_up_fwd': [vp, vp] + [i32] * 6 + [vp],
     'mlc_bilinear_up_bwd': [vp, vp] + [i32] * 6 + [vp],
     'mlc_gn_relu_fwd': [vp, vp, vp, vp, vp] + [i32] * 4 + [f32, vp],

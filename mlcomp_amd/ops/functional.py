@@ -301,15 +301,24 @@ class WtTable:
 
 def conv2d_dgrad(dy: torch.Tensor, w: torch.Tensor, x_shape, stride=1, pad=0, dil=1,
                  addend: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-                 bn: Optional[BnBwdSpec] = None, wt: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 bn: Optional[BnBwdSpec] = None, wt: Optional[torch.Tensor] = None,
+                 strided_addend: Optional[Tuple[torch.Tensor, int]] = None) -> torch.Tensor:
     """dx = conv_transpose(dy, w) [+ addend] (the addend fuses the gradient sum of a
     residual branch point into the epilogue; ``out`` may alias ``addend``).  With ``bn``
     the epilogue also masks dx by ``bn.mask > 0`` and accumulates the BN-backward sums.
     ``wt`` (= :func:`wt_flip_transpose` of ``w``): read the filter operand K-contiguous
-    from it (stride 1: the equivalent forward conv, :func:`dgrad_as_fwd_conv`)."""
+    from it (stride 1: the equivalent forward conv, :func:`dgrad_as_fwd_conv`).
+    ``strided_addend = (t, S)`` instead of ``addend``: ``t`` is the compact
+    [N, (H-1)//S + 1, (W-1)//S + 1, C] tensor added at ``dx[:, ::S, ::S]`` (the input gradient
+    of a 1x1 / stride-S / pad-0 shortcut conv, never expanded); ``out`` must not alias it."""
     N, H, W, C = x_shape
     Co, KH, KW, Ci = w.shape
     _, Ho, Wo, _ = dy.shape
+    if strided_addend is not None:
+        assert addend is None, 'one addend form at a time'
+        sadd, S = strided_addend
+        assert S >= 1 and tuple(sadd.shape) == (N, (H - 1) // S + 1, (W - 1) // S + 1, C), (sadd.shape, x_shape, S)
+        assert sadd.is_contiguous() and (out is None or out.data_ptr() != sadd.data_ptr())
     if _cuda(dy):
         dx = out if out is not None else torch.empty(N, H, W, C, device=dy.device, dtype=torch.bfloat16)
         b = [None] * 11
@@ -319,13 +328,15 @@ def conv2d_dgrad(dy: torch.Tensor, w: torch.Tensor, x_shape, stride=1, pad=0, di
                 b[1 + 3 * k:4 + 3 * k] = [yk, mk, sk]
             for k, (ak, hk) in enumerate(bn.affine or []):
                 b[7 + 2 * k:9 + 2 * k] = [ak, hk]
+        name, filt = 'mlc_conv_dgrad', w
         if wt is not None:
             assert tuple(wt.shape) == (Ci, KH, KW, Co), (wt.shape, w.shape)
-            _lib.call('mlc_conv_dgrad_t', _lib.ptr(dy), _lib.ptr(wt), _lib.ptr(dx), _lib.ptr(addend), N, H, W,
-                      C, Co, KH, KW, stride, pack_pad(pad), dil, Ho, Wo, *[_lib.ptr(t) for t in b], _lib.stream())
-            return dx
-        _lib.call('mlc_conv_dgrad', _lib.ptr(dy), _lib.ptr(w), _lib.ptr(dx), _lib.ptr(addend), N, H, W, C,
-                  Co, KH, KW, stride, pack_pad(pad), dil, Ho, Wo, *[_lib.ptr(t) for t in b], _lib.stream())
+            name, filt = 'mlc_conv_dgrad_t', wt
+        add = [_lib.ptr(addend)]
+        if strided_addend is not None:
+            name, add = name + '_sadd', [None, _lib.ptr(sadd), S]
+        _lib.call(name, _lib.ptr(dy), _lib.ptr(filt), _lib.ptr(dx), *add, N, H, W, C, Co, KH, KW, stride,
+                  pack_pad(pad), dil, Ho, Wo, *[_lib.ptr(t) for t in b], _lib.stream())
         return dx
     if wt is not None and isinstance(pad, int) and dgrad_as_fwd_conv(KH, KW, stride, pad, dil):   # fwd conv over wt
         dxf = F.conv2d(dy.permute(0, 3, 1, 2).float(), wt.permute(0, 3, 1, 2).float(), None, 1,
@@ -338,6 +349,9 @@ def conv2d_dgrad(dy: torch.Tensor, w: torch.Tensor, x_shape, stride=1, pad=0, di
     dxf = dxf.permute(0, 2, 3, 1)
     if addend is not None:
         dxf = dxf + addend.float()
+    if strided_addend is not None:
+        dxf = dxf.contiguous()
+        dxf[:, ::S, ::S, :] += sadd.float()
     if bn is not None:
         if bn.mask is not None:
             dxf = dxf * (bn.mask.float() > 0)

@@ -31,6 +31,12 @@ from .arena import ParamArena, Slot
 # (profiles/round3/README.md): U-Net +1.8 % with dgrad first, ResNet-50 -1 %, BERT-base -3 %.
 # Unset: the engine's default (NativeContext.dgrad_first; the U-Net engine turns it on).
 DGRAD_FIRST_ENV = os.environ.get('MLC_DGRAD_FIRST')
+# MLC_COMPACT_SHORTCUT_GRAD=1 (default): the input gradient of a residual block's 1x1 /
+# strided / pad-0 shortcut conv stays compact, [N, Ho, Wo, C]: one stride-1 GEMM instead of
+# one per stride-parity class (all but one of which only write zeros), and the first unit's
+# dgrad epilogue adds it at the pixels it covers (Fn.conv2d_dgrad strided_addend).  0: the
+# shortcut's dgrad writes the full-resolution tensor, which is read back as the addend.
+COMPACT_SHORTCUT_GRAD = os.environ.get('MLC_COMPACT_SHORTCUT_GRAD', '1') == '1'
 
 
 class Workspace:
@@ -374,15 +380,27 @@ class ConvBN:
             return False
         return Fn.conv1x1_fwd_res_available(self.cin_p, self.Co)
 
-    def _dgrad(self, dy, x_shape, addend=None, out=None, bn=None):
+    def _dgrad(self, dy, x_shape, addend=None, out=None, bn=None, saddend=None, compact=False):
         wt = None
         if self.wt_idx is not None:
             if self.ctx.wt_stale:
                 raise RuntimeError('transposed filters are stale: the model must call '
                                    'ctx.refresh_wt() after its training forward pass')
             wt = self.ctx.wt[self.wt_idx]
+        if compact:
+            # dx at the pixels the strided 1x1 conv reads, [N, Ho, Wo, C]: the stride-1 dgrad of
+            # the same filter over dy's own grid (every other dx pixel is zero)
+            assert self.compact_dx() and addend is None and saddend is None and bn is None
+            return Fn.conv2d_dgrad(dy, self.w.bf16, tuple(dy.shape[:3]) + (x_shape[3],), out=out, wt=wt)
         return Fn.conv2d_dgrad(dy, self.w.bf16, x_shape, self.stride, self.pad, self.dil,
-                               addend=addend, out=out, bn=bn, wt=wt)
+                               addend=addend, out=out, bn=bn, wt=wt, strided_addend=saddend)
+
+    def compact_dx(self) -> bool:
+        """True when ``bwd(..., compact_dx=True)`` may return the input gradient without its
+        structural zeros (MLC_COMPACT_SHORTCUT_GRAD): a plain 1x1 / strided / pad-0 conv,
+        whose dx is non-zero only at ``[:, ::stride, ::stride]``."""
+        return (COMPACT_SHORTCUT_GRAD and type(self) is ConvBN and not self.s2d and self.k == (1, 1)
+                and self.pad == 0 and self.dil == 1 and self.stride > 1)
 
     def dgrad_covers_all(self) -> bool:
         """True when the dgrad GEMM epilogue writes every dx row, i.e. a BN-backward
@@ -420,13 +438,19 @@ class ConvBN:
         return Fn.conv1x1_bn_bwd_available(self.cin_p, self.Co)
 
     def bwd(self, dz, rec, want_dres=False, dx_addend=None, need_dx=True, dx_out=None,
-            prereduced=False, dgrad_bn=None, in_affine=None, defer: Optional[list] = None):
+            prereduced=False, dgrad_bn=None, in_affine=None, defer: Optional[list] = None,
+            dx_saddend=None, compact_dx=False):
         """``defer`` (with a wgrad stream): leave the weight gradient running on the side
         stream; (dy, x, weight slot) is appended so the caller keeps the tensors alive, joins
-        the stream later and then marks the slot ready."""
+        the stream later and then marks the slot ready.
+        ``dx_saddend = (t, S)``: the addend in its compact strided form (``Fn.conv2d_dgrad``),
+        instead of ``dx_addend``.  ``compact_dx`` (where :meth:`compact_dx` allows it): dx is
+        returned without its structural zeros, [N, Ho, Wo, C], for a consumer that takes it as
+        ``dx_saddend = (dx, stride)``; the weight gradient and the BN backward are the same."""
         x, y, z = rec
         arena = self.ctx.arena
-        if need_dx and prereduced and in_affine is None and self._fused_1x1_bwd_ok(dz, x, dgrad_bn):
+        if need_dx and prereduced and in_affine is None and dx_saddend is None \
+                and self._fused_1x1_bwd_ok(dz, x, dgrad_bn):
             # one kernel: BN-backward apply + dgrad + wgrad (Fn.conv1x1_bn_bwd); dy is never
             # written, so there is no side-stream weight gradient to fork, defer or join
             if not self.ctx.grad_prezeroed:
@@ -460,7 +484,8 @@ class ConvBN:
             self.wgrad(dy, x, in_affine)
         dx = None
         if need_dx:
-            dx = self._dgrad(dy, x.shape, addend=dx_addend, out=dx_out, bn=dgrad_bn)
+            dx = self._dgrad(dy, x.shape, addend=dx_addend, out=dx_out, bn=dgrad_bn, saddend=dx_saddend,
+                             compact=compact_dx)
         if side is not None and self.ctx.dgrad_first:
             # captured after the dgrad but forked from the point before it: the dgrad is the
             # first child of the previous node, so graph replay keeps the dgrad -> BN chain
@@ -554,8 +579,9 @@ class ConvTBN(ConvBN):
         return Fn.conv_transpose2d_fwd(x, self.w.bf16, self.out_hw(x.shape[1], x.shape[2]), self.stride,
                                        self.pad, self.dil, stats=stats)
 
-    def _dgrad(self, dy, x_shape, addend=None, out=None, bn=None):
-        assert addend is None and out is None and bn is None, 'ConvTBN input gradient: plain conv'
+    def _dgrad(self, dy, x_shape, addend=None, out=None, bn=None, saddend=None, compact=False):
+        assert addend is None and out is None and bn is None and saddend is None and not compact, \
+            'ConvTBN input gradient: plain conv'
         dx = Fn.conv2d_fwd(dy, self.w.bf16, self.stride, self.pad, self.dil)
         assert tuple(dx.shape) == tuple(x_shape), (dx.shape, x_shape)
         return dx
@@ -742,12 +768,18 @@ class _ResidualBlockFn(torch.autograd.Function):
         # becomes the first unit's dgrad output) and the streams join before that dgrad
         down_side = side if (blk.down is not None and pend is None and blk.down_stream) else None
         short = dres
+        # a 1x1 / strided / pad-0 shortcut hands its input gradient over compact, [N, Ho, Wo, C]
+        # (MLC_COMPACT_SHORTCUT_GRAD): the first unit's dgrad adds it at the pixels it covers
+        # and writes dx to a buffer of its own
+        compact = need_dx and blk.down is not None and blk.down.compact_dx()
         if down_side is not None:
             main = torch.cuda.current_stream(units[0].ctx.device)
-            short_buf = torch.empty(rd[0].shape, device=rd[0].device, dtype=rd[0].dtype) if need_dx else None
+            short_shape = tuple(dres.shape[:3]) + (rd[0].shape[3],) if compact else rd[0].shape
+            short_buf = torch.empty(short_shape, device=rd[0].device, dtype=rd[0].dtype) if need_dx else None
             down_side.wait_stream(main)
             with Fn.side_stream(down_side):
-                short, _ = blk.down.bwd(dres, rd, need_dx=need_dx, prereduced=pre, dx_out=short_buf)
+                short, _ = blk.down.bwd(dres, rd, need_dx=need_dx, prereduced=pre, dx_out=short_buf,
+                                        compact_dx=compact)
         for i in range(len(units) - 2, 0, -1):
             sp = spec_for(i - 1)
             d, _ = units[i].bwd(d, recs[i], prereduced=fused, dgrad_bn=sp, in_affine=affs[i], defer=pend)
@@ -756,14 +788,18 @@ class _ResidualBlockFn(torch.autograd.Function):
             main.wait_stream(down_side)
         elif blk.down is not None:
             # shortcut conv first; its dx becomes the addend of the first unit's dgrad
-            short, _ = blk.down.bwd(dres, rd, need_dx=need_dx, prereduced=pre, defer=pend)
+            short, _ = blk.down.bwd(dres, rd, need_dx=need_dx, prereduced=pre, defer=pend, compact_dx=compact)
         prev_spec = None
         if need_dx and fuse and blk.prev is not None and blk.prev._last is not None \
                 and units[0].dgrad_covers_all():
             prev_spec = blk.prev.output_bn_spec()
-        dx, _ = units[0].bwd(d, recs[0], dx_addend=short if need_dx else None, need_dx=need_dx,
-                             dx_out=short if (need_dx and blk.down is not None) else None,
-                             prereduced=fused, dgrad_bn=prev_spec, defer=pend)
+        if compact:
+            dx, _ = units[0].bwd(d, recs[0], dx_saddend=(short, blk.down.stride), need_dx=need_dx,
+                                 prereduced=fused, dgrad_bn=prev_spec, defer=pend)
+        else:
+            dx, _ = units[0].bwd(d, recs[0], dx_addend=short if need_dx else None, need_dx=need_dx,
+                                 dx_out=short if (need_dx and blk.down is not None) else None,
+                                 prereduced=fused, dgrad_bn=prev_spec, defer=pend)
         if prev_spec is not None:
             blk.prev.dout_prereduced = True
         if pend:
