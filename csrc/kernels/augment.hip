@@ -255,6 +255,95 @@ augment_seg_pix_kernel(const uint8_t* __restrict__ src, const uint8_t* __restric
   }
 }
 
+// ---- video clips: one box and one flip for every frame of a clip (mlc_augment_clip) ----
+// par: per clip {y0, x0, h, w, flip, t0, frame stride, 0}; t0 and the stride say which
+// frames of the record the host gathered and are not read here.  The box is clamped into
+// the image as seg_box does, so no par can make a thread read outside its clip.
+__device__ __forceinline__ Box clip_box(const int* par, int b, int H, int W, int oh, int ow) {
+  const int* p = par + 8 * b;
+  const int y0 = min(max(p[0], 0), H - 1), x0 = min(max(p[1], 0), W - 1);
+  Box r;
+  r.h = min(max(p[2], 1), H - y0);
+  r.w = min(max(p[3], 1), W - x0);
+  r.y0 = (float)y0; r.x0 = (float)x0; r.flip = p[4];
+  r.sy = (float)r.h / (float)oh;
+  r.sx = (float)r.w / (float)ow;
+  return r;
+}
+
+// one bf16 pixel of 3 channels at flattened pixel index g (6 bytes): a dword and a short,
+// in the order that keeps the dword aligned
+__device__ __forceinline__ void store_px3(bf16* out, long g, const float* v) {
+  bf16* o = out + g * 3;
+  if (g & 1) {
+    o[0] = f2bf(v[0]);
+    *reinterpret_cast<uint32_t*>(o + 1) = pack2_bf16(v[1], v[2]);
+  } else {
+    *reinterpret_cast<uint32_t*>(o) = pack2_bf16(v[0], v[1]);
+    o[2] = f2bf(v[2]);
+  }
+}
+
+// L = 0: fp32 [B][C][T][oh][ow];  L = 1: bf16 [B][T][oh][ow][C], exactly C channels.
+// A thread owns NP output pixels of a clip (two adjacent ones of the 3-channel bf16 form,
+// stored as three dwords where the flattened pixel index is even) and loops over the T
+// frames: the sample position does not depend on the frame, so the clamped coordinates,
+// the four tap offsets and the two weights of sample_at are loop invariants and a frame
+// costs 4*C byte loads at a stride of H*W*C plus the store.
+template <int C, int L>
+__global__ void __launch_bounds__(NT)
+augment_clip_kernel(const uint8_t* __restrict__ src, const int* __restrict__ par, const float* __restrict__ ms,
+                    void* __restrict__ out, int B, int T, int H, int W, int oh, int ow) {
+  constexpr int NP = (L == 1 && C == 3) ? 2 : 1;
+  const long px = (long)oh * ow;   // pixels of a frame
+  const long groups = (px + NP - 1) / NP;
+  const long total = (long)B * groups;
+  const size_t fb = (size_t)H * W * C;
+  for (long q = (long)blockIdx.x * NT + threadIdx.x; q < total; q += (long)gridDim.x * NT) {
+    const long pix = (q % groups) * NP;
+    const int b = (int)(q / groups);
+    const Box bx = clip_box(par, b, H, W, oh, ow);
+    const bool two = NP == 2 && pix + 1 < px;
+    const int oy0 = (int)(pix / ow), ox0 = (int)(pix % ow);
+    const int oy1 = (int)((pix + 1) / ow), ox1 = (int)((pix + 1) % ow);
+    const uint8_t* img = src + (size_t)b * T * fb;
+    for (int t = 0; t < T; ++t, img += fb) {
+      float f[C], v[NP][C];
+      sample<C>(img, W, bx, oy0, ox0, ow, f);
+#pragma unroll
+      for (int c = 0; c < C; ++c) v[0][c] = (f[c] - ms[c]) * ms[4 + c];
+      if constexpr (NP == 2) if (two) {
+        sample<C>(img, W, bx, oy1, ox1, ow, f);
+#pragma unroll
+        for (int c = 0; c < C; ++c) v[NP - 1][c] = (f[c] - ms[c]) * ms[4 + c];
+      }
+      if constexpr (L == 0) {
+        float* o = reinterpret_cast<float*>(out);
+#pragma unroll
+        for (int c = 0; c < C; ++c) o[(((size_t)b * C + c) * T + t) * px + pix] = v[0][c];
+      } else {
+        bf16* o = reinterpret_cast<bf16*>(out);
+        const long g = ((long)b * T + t) * px + pix;   // flattened pixel index
+        if constexpr (C == 1) {
+          o[g] = f2bf(v[0][0]);
+        } else if constexpr (C == 2) {
+          reinterpret_cast<uint32_t*>(o)[g] = pack2_bf16(v[0][0], v[0][1]);
+        } else if constexpr (C == 4) {
+          reinterpret_cast<uint2*>(o)[g] = make_uint2(pack2_bf16(v[0][0], v[0][1]), pack2_bf16(v[0][2], v[0][3]));
+        } else if (two && !(g & 1)) {
+          uint32_t* d = reinterpret_cast<uint32_t*>(o + g * 3);
+          d[0] = pack2_bf16(v[0][0], v[0][1]);
+          d[1] = pack2_bf16(v[0][2], v[NP - 1][0]);
+          d[2] = pack2_bf16(v[NP - 1][1], v[NP - 1][2]);
+        } else {
+          store_px3(o, g, v[0]);
+          if (two) store_px3(o, g + 1, v[NP - 1]);
+        }
+      }
+    }
+  }
+}
+
 }  // namespace
 
 // mean_istd: 8 floats {mean[0..3], 1/std[0..3]} (uint8 scale) on the device
@@ -314,5 +403,36 @@ MLC_EXPORT int mlc_augment_seg(const uint8_t* img, const uint8_t* mask, const in
   else if (C == 3) AUG_SEG(3);
   else AUG_SEG(4);
 #undef AUG_SEG
+  return hipGetLastError();
+}
+
+// Video clips: src uint8 [B][T][H][W][C] (the frames the host gathered), par int32 [B][8] =
+// {y0, x0, h, w, flip, t0, frame stride, 0} on the device, one transform per clip.
+// layout 0: fp32 [B][C][T][oh][ow] (NCTHW); layout 1: bf16 [B][T][oh][ow][C] with exactly
+// C channels (the channels_last_3d storage of a [B, C, T, oh, ow] tensor).  One launch; per
+// frame the arithmetic is mlc_augment's, so the values are the same bits.  Returns -1 for
+// arguments out of range; the boxes are clamped into the image by the kernel.
+MLC_EXPORT int mlc_augment_clip(const uint8_t* src, const int* par, const float* mean_istd, void* out, int B, int T,
+                                int H, int W, int C, int oh, int ow, int layout, hipStream_t st) {
+  if (C < 1 || C > 4 || B <= 0 || T <= 0 || H <= 0 || W <= 0 || oh <= 0 || ow <= 0 || layout < 0 || layout > 1)
+    return -1;
+  if (!src || !par || !mean_istd || !out) return -1;
+  const long px = (long)oh * ow;
+  const long total = (long)B * (layout == 1 && C == 3 ? (px + 1) / 2 : px);
+  long blocks = (total + NT - 1) / NT;
+  if (blocks > 16384) blocks = 16384;
+#define AUG_CLIP(CC, LL) hipLaunchKernelGGL((augment_clip_kernel<CC, LL>), dim3((int)blocks), dim3(NT), 0, st, src, \
+                                            par, mean_istd, out, B, T, H, W, oh, ow)
+#define AUG_CLIP_C(LL) \
+  do {                 \
+    if (C == 1) AUG_CLIP(1, LL); \
+    else if (C == 2) AUG_CLIP(2, LL); \
+    else if (C == 3) AUG_CLIP(3, LL); \
+    else AUG_CLIP(4, LL); \
+  } while (0)
+  if (layout == 0) AUG_CLIP_C(0);
+  else AUG_CLIP_C(1);
+#undef AUG_CLIP_C
+#undef AUG_CLIP
   return hipGetLastError();
 }

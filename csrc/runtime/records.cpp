@@ -27,6 +27,15 @@
 // {y0, x0, h, w, hflip, vflip, transpose, 0}: the box draws are the classification ones,
 // then three independent coins that span the eight symmetries of the square.
 //
+// Video clip files: magic "MLVID001", label_bytes = 4, record_bytes = F*H*W*C + 4,
+// reserved[0..3] = u32 F (frames per record, >= 1, fixed per file); records
+// {u8 frames[F][H][W][C]; i32 label}.  The clip loader (mlr_clip_*) has a clip length T and
+// a frame stride s with span = (T-1)*s + 1 <= F.  It draws the box and the flip exactly as
+// the classification loader does (one transform for every frame of a clip), then the first
+// frame t0 = r % (F - span + 1) (evaluation: the centre, (F - span) / 2);
+// params[batch][8] = {y0, x0, h, w, flip, t0, s, 0}.  The gather threads copy only the T
+// frames t0 + k*s, so a slot's image buffer is [batch][T][H][W][C].
+//
 // Slot protocol: the caller registers `depth` slots (image buffer of batch*H*W*C bytes,
 // int64 labels[batch], int32 params[batch][5]); next() blocks until the next batch of the
 // epoch (in order) is complete and returns its slot, release(slot) hands it back.  Batches
@@ -52,6 +61,9 @@ namespace {
 
 constexpr char MAGIC[8] = {'M', 'L', 'R', 'E', 'C', '0', '0', '1'};
 constexpr char SEG_MAGIC[8] = {'M', 'L', 'S', 'E', 'G', '0', '0', '1'};
+constexpr char CLIP_MAGIC[8] = {'M', 'L', 'V', 'I', 'D', '0', '0', '1'};
+
+enum Kind { LABELS = 0, SEG = 1, CLIP = 2 };   // what a record holds next to its image(s)
 
 struct Header {
   char magic[8];
@@ -67,6 +79,8 @@ struct RecordFile {
   size_t size = 0;
   Header h{};
   uint32_t K = 0, kind = 0;   // mask planes and kind of a segmentation file (K = 0: labels)
+  uint32_t F = 0;             // frames per record of a clip file (0: not a clip file)
+  Kind what() const { return F ? CLIP : K ? SEG : LABELS; }
   const uint8_t* record(uint64_t i) const { return map + sizeof(Header) + i * h.record_bytes; }
 };
 
@@ -105,6 +119,8 @@ struct Loader {
   int rank, world, shuffle, drop_last;
   int chunk = 16;
   bool seg = false;   // image + mask records, params[batch][8]
+  bool clip = false;  // clip records: clip_len frames at frame_stride, params[batch][8]
+  int clip_len = 0, frame_stride = 1;
   std::vector<Slot> slots;
   // epoch
   uint64_t epoch = 0;
@@ -118,10 +134,11 @@ struct Loader {
 
   int chunks_per_batch() const { return (batch + chunk - 1) / chunk; }
 
-  int par_stride() const { return seg ? 8 : 5; }
+  int par_stride() const { return seg || clip ? 8 : 5; }
+  int span() const { return (clip_len - 1) * frame_stride + 1; }
 
-  // one sample's augmentation: the source box {y0, x0, h, w}, then {flip} or, for
-  // segmentation, {hflip, vflip, transpose, 0}
+  // one sample's augmentation: the source box {y0, x0, h, w}, then {flip}, for
+  // segmentation {hflip, vflip, transpose, 0}, for clips {flip, t0, frame stride, 0}
   void params(uint64_t sample, int32_t* p) const {
     const int H = (int)rf->h.H, W = (int)rf->h.W;
     Rng g(seed * 0x100000001b3ull ^ (epoch << 40) ^ sample);
@@ -129,11 +146,16 @@ struct Loader {
     if (!train) {   // centre crop of the output size (whole image if it is smaller)
       const int h = std::min(H, out_h), w = std::min(W, out_w);
       p[0] = (H - h) / 2; p[1] = (W - w) / 2; p[2] = h; p[3] = w;
+      if (clip) { p[5] = ((int)rf->F - span()) / 2; p[6] = frame_stride; }
       return;
     }
     draw_box(g, H, W, p);
     const int coins = seg ? 3 : 1;
     for (int i = 0; i < coins; ++i) p[4 + i] = (int)(g.next() & 1);
+    if (clip) {   // after the classification draws, so the box and the flip are the image loader's
+      p[5] = (int)(g.next() % (uint64_t)((int)rf->F - span() + 1));
+      p[6] = frame_stride;
+    }
   }
 
   void draw_box(Rng& g, int H, int W, int32_t* p) const {
@@ -161,6 +183,16 @@ struct Loader {
     for (int i = i0; i < i1; ++i) {
       const uint64_t s = order[(size_t)b * batch + i];
       const uint8_t* rec = rf->record(s);
+      if (clip) {   // only the selected frames t0 + k*stride cross into the slot
+        int32_t* p = sl.par + par_stride() * i;
+        params(s, p);
+        for (int k = 0; k < clip_len; ++k)
+          std::memcpy(sl.img + ((size_t)i * clip_len + k) * ib, rec + (size_t)(p[5] + k * p[6]) * ib, ib);
+        int32_t lab;
+        std::memcpy(&lab, rec + (size_t)rf->F * ib, 4);
+        sl.lab[i] = lab;
+        continue;
+      }
       std::memcpy(sl.img + (size_t)i * ib, rec, ib);
       if (seg) {
         std::memcpy(sl.mask + (size_t)i * mb, rec + ib, mb);
@@ -269,7 +301,7 @@ struct Loader {
 
 namespace {
 
-RecordFile* open_file(const char* path, bool seg) {
+RecordFile* open_file(const char* path, Kind kind) {
   auto* rf = new RecordFile();
   rf->fd = open(path, O_RDONLY);
   struct stat st{};
@@ -286,7 +318,11 @@ RecordFile* open_file(const char* path, bool seg) {
   const uint64_t need = sizeof(Header) + rf->h.count * rf->h.record_bytes;
   const uint64_t ib = (uint64_t)rf->h.H * rf->h.W * rf->h.C;
   bool ok;
-  if (seg) {
+  if (kind == CLIP) {
+    std::memcpy(&rf->F, rf->h.reserved, 4);
+    ok = std::memcmp(rf->h.magic, CLIP_MAGIC, 8) == 0 && rf->F >= 1 && rf->h.C >= 1 && rf->h.C <= 4 &&
+         rf->h.label_bytes == 4 && rf->h.record_bytes == (uint64_t)rf->F * ib + 4;
+  } else if (kind == SEG) {
     std::memcpy(&rf->K, rf->h.reserved, 4);
     std::memcpy(&rf->kind, rf->h.reserved + 4, 4);
     const uint64_t mb = (uint64_t)rf->h.H * rf->h.W * rf->K;
@@ -306,14 +342,20 @@ RecordFile* open_file(const char* path, bool seg) {
   return rf;
 }
 
-Loader* create_loader(void* file, bool seg, int batch, int out_h, int out_w, int train, double smin, double smax,
+Loader* create_loader(void* file, Kind kind, int batch, int out_h, int out_w, int train, double smin, double smax,
                       double rmin, double rmax, uint64_t seed, int rank, int world, int shuffle, int drop_last,
-                      int threads, int chunk) {
+                      int threads, int chunk, int clip_len = 0, int frame_stride = 1) {
   if (!file || batch <= 0 || world <= 0 || rank < 0 || rank >= world || threads <= 0) return nullptr;
-  if ((((const RecordFile*)file)->K != 0) != seg) return nullptr;   // the other kind of file
+  if (((const RecordFile*)file)->what() != kind) return nullptr;   // another kind of file
+  if (kind == CLIP) {   // the clip's span (T-1)*s + 1 has to fit into the record's F frames
+    const int64_t F = ((const RecordFile*)file)->F;
+    if (clip_len <= 0 || frame_stride <= 0 || (int64_t)(clip_len - 1) * frame_stride + 1 > F) return nullptr;
+  }
   auto* L = new Loader();
   L->rf = (const RecordFile*)file;
-  L->seg = seg;
+  L->seg = kind == SEG;
+  L->clip = kind == CLIP;
+  L->clip_len = clip_len; L->frame_stride = frame_stride;
   L->batch = batch; L->out_h = out_h; L->out_w = out_w; L->train = train;
   L->smin = smin; L->smax = smax; L->rmin = rmin; L->rmax = rmax;
   L->seed = seed; L->rank = rank; L->world = world; L->shuffle = shuffle; L->drop_last = drop_last;
@@ -335,10 +377,20 @@ int set_slot(Loader* L, int i, uint8_t* img, int64_t* lab, uint8_t* mask, int32_
 
 }  // namespace
 
-MLR_EXPORT void* mlr_open(const char* path) { return open_file(path, false); }
+MLR_EXPORT void* mlr_open(const char* path) { return open_file(path, LABELS); }
 
 // an image + mask file; closed with mlr_close
-MLR_EXPORT void* mlr_seg_open(const char* path) { return open_file(path, true); }
+MLR_EXPORT void* mlr_seg_open(const char* path) { return open_file(path, SEG); }
+
+// a clip file; closed with mlr_close
+MLR_EXPORT void* mlr_clip_open(const char* path) { return open_file(path, CLIP); }
+
+// shape[0..4] = count, H, W, C, F
+MLR_EXPORT void mlr_clip_shape(void* h, uint64_t* shape) {
+  const auto* rf = (const RecordFile*)h;
+  shape[0] = rf->h.count; shape[1] = rf->h.H; shape[2] = rf->h.W; shape[3] = rf->h.C;
+  shape[4] = rf->F;
+}
 
 // shape[0..5] = count, H, W, C, K, kind
 MLR_EXPORT void mlr_seg_shape(void* h, uint64_t* shape) {
@@ -365,7 +417,7 @@ MLR_EXPORT void mlr_close(void* h) {
 MLR_EXPORT void* mlr_loader_create(void* file, int batch, int out_h, int out_w, int train, double smin, double smax,
                                    double rmin, double rmax, uint64_t seed, int rank, int world, int shuffle,
                                    int drop_last, int threads, int chunk) {
-  return create_loader(file, false, batch, out_h, out_w, train, smin, smax, rmin, rmax, seed, rank, world, shuffle,
+  return create_loader(file, LABELS, batch, out_h, out_w, train, smin, smax, rmin, rmax, seed, rank, world, shuffle,
                        drop_last, threads, chunk);
 }
 
@@ -379,7 +431,7 @@ MLR_EXPORT int mlr_loader_set_slot(void* h, int i, uint8_t* img, int64_t* lab, i
 MLR_EXPORT void* mlr_seg_loader_create(void* file, int batch, int out_h, int out_w, int train, double smin,
                                        double smax, double rmin, double rmax, uint64_t seed, int rank, int world,
                                        int shuffle, int drop_last, int threads, int chunk) {
-  return create_loader(file, true, batch, out_h, out_w, train, smin, smax, rmin, rmax, seed, rank, world, shuffle,
+  return create_loader(file, SEG, batch, out_h, out_w, train, smin, smax, rmin, rmax, seed, rank, world, shuffle,
                        drop_last, threads, chunk);
 }
 
@@ -388,6 +440,25 @@ MLR_EXPORT int mlr_seg_loader_set_slot(void* h, int i, uint8_t* img, uint8_t* ma
   auto* L = (Loader*)h;
   if (!L->seg) return -1;
   return set_slot(L, i, img, nullptr, mask, par);
+}
+
+// the loader of an mlr_clip_open file: clips of `clip_len` frames `frame_stride` apart, one
+// box and flip per clip (the mlr_loader_create draws) and then the first frame t0; null if
+// (clip_len-1)*frame_stride + 1 exceeds the file's frames per record; start_epoch / next /
+// release / destroy are the mlr_loader_* ones
+MLR_EXPORT void* mlr_clip_loader_create(void* file, int batch, int out_h, int out_w, int clip_len, int frame_stride,
+                                        int train, double smin, double smax, double rmin, double rmax,
+                                        uint64_t seed, int rank, int world, int shuffle, int drop_last,
+                                        int threads, int chunk) {
+  return create_loader(file, CLIP, batch, out_h, out_w, train, smin, smax, rmin, rmax, seed, rank, world, shuffle,
+                       drop_last, threads, chunk, clip_len, frame_stride);
+}
+
+// slot `i`: image batch*clip_len*H*W*C bytes, int64 labels[batch], int32 par[batch][8]
+MLR_EXPORT int mlr_clip_loader_set_slot(void* h, int i, uint8_t* img, int64_t* lab, int32_t* par) {
+  auto* L = (Loader*)h;
+  if (!L->clip) return -1;
+  return set_slot(L, i, img, lab, nullptr, par);
 }
 
 // (re)start at `epoch`; returns the number of batches this rank yields in it

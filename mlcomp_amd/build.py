@@ -11,9 +11,9 @@
   launched at `mlcomp/server/__main__.py:66-79`).
 * ``libmlcomp_runtime.so`` - host-side C++ runtime (``csrc/runtime``): the memory-mapped
   record files and the threaded batch gatherer of the native input pipeline
-  (:mod:`mlcomp_amd.train.records`); ``mlcomp-records-selftest-<san>`` and
-  ``mlcomp-records-seg-selftest-<san>`` are its ThreadSanitizer / AddressSanitizer
-  self-tests.
+  (:mod:`mlcomp_amd.train.records`); ``mlcomp-records-selftest-<san>``,
+  ``mlcomp-records-seg-selftest-<san>`` and ``mlcomp-records-clip-selftest-<san>`` are its
+  ThreadSanitizer / AddressSanitizer self-tests.
 
 Outputs live under ``mlcomp_amd/_native/`` so they travel with the repo snapshot.
 Compilation is incremental (mtime based) and parallel.
@@ -144,7 +144,7 @@ def build_runtime(verbose=False):
 
 def build_runtime_selftest(sanitize='tsan', verbose=False, main='records_selftest.cpp'):
     """A record loader self-test driver (``main``, a file of ``csrc/runtime``:
-    ``records_selftest.cpp`` or ``records_seg_selftest.cpp``) linked with an instrumented
+    ``records_selftest.cpp``, ``records_seg_selftest.cpp`` or ``records_clip_selftest.cpp``) linked with an instrumented
     copy of the runtime sources (``tsan``: ThreadSanitizer, ``asan``: AddressSanitizer +
     UBSan)."""
     os.makedirs(OUT, exist_ok=True)

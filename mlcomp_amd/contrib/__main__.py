@@ -134,5 +134,45 @@ def pack_seg_records(img_path, mask_path, out, size, kind, fold_csv, fold, exclu
     click.echo(f'{n} image / mask pairs ({kind}) -> {out}')
 
 
+@main.command('pack-clip-records')
+@click.option('--video-path', required=True, help='class/video/frames tree, or the root of the fold.csv video column')
+@click.option('--out', required=True, help='the clip record file to write')
+@click.option('--frames', type=int, required=True, help='frames stored per record')
+@click.option('--size', type=int, default=128, help='stored square size (shorter side resized, centre crop)')
+@click.option('--frame-step', type=int, default=1, help='take every n-th frame file of a folder')
+@click.option('--pad-short', is_flag=True, help='repeat the last frame of a folder with too few frames')
+@click.option('--fold-csv', default=None, help='fold.csv (video,label,fold): pack the rows of --fold only')
+@click.option('--fold', type=int, default=None)
+@click.option('--exclude-fold', is_flag=True, help='pack every fold except --fold (the training split)')
+def pack_clip_records(video_path, out, frames, size, frame_step, pad_short, fold_csv, fold, exclude_fold):
+    """Pack a class/video/frames tree of frame images (or the rows of a fold.csv, as
+    VideoDataset reads them) into a clip record file for the native input pipeline
+    (mlcomp_amd.train.records): per video the centred window of --frames frames."""
+    from mlcomp_amd.train.records import pack_clip_frames
+    if fold_csv:
+        import pandas as pd
+        df = pd.read_csv(fold_csv)
+        if fold is not None:
+            df = df[(df['fold'] != fold) if exclude_fold else (df['fold'] == fold)]
+        names = sorted(df['label'].astype(str).unique())
+        dirs = [join(video_path, p) for p in df['video']]
+        labels = [names.index(str(v)) for v in df['label']]
+    else:
+        names = sorted(d for d in os.listdir(video_path) if os.path.isdir(join(video_path, d)))
+        pairs = [(join(video_path, d, v), i) for i, d in enumerate(names)
+                 for v in sorted(os.listdir(join(video_path, d))) if os.path.isdir(join(video_path, d, v))]
+        dirs, labels = [p for p, _ in pairs], [lab for _, lab in pairs]
+    if not dirs:
+        raise click.ClickException('no video folders')
+    try:
+        n = pack_clip_frames(dirs, labels, out, frames=frames, size=size, frame_step=frame_step,
+                             pad_short=pad_short)
+    except ValueError as e:
+        raise click.ClickException(str(e))
+    with open(out + '.classes', 'w') as f:
+        f.write('\n'.join(names) + '\n')
+    click.echo(f'{n} clips of {frames} frames, {len(names)} classes -> {out}')
+
+
 if __name__ == '__main__':
     main()

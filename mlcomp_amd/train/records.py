@@ -22,6 +22,13 @@ split between the host and the GPU instead.
   hflip / vflip / transpose coins (the eight symmetries of the square) and one kernel
   (``mlc_augment_seg``) samples the image bilinearly and the mask by nearest neighbour at
   the same source coordinate.  :func:`augment_seg_reference` is its PyTorch twin.
+* Video: ``MLVID001`` files hold clips of F uint8 frames and an int32 label
+  (:func:`write_clip_records`, :func:`pack_clip_frames`, :class:`ClipRecordFile`).
+  :class:`ClipRecordLoader` runs the same ring over them: the host draws one box and flip per
+  clip (the classification draws) and the first frame ``t0``, copies only the ``clip_len``
+  frames ``t0 + k*frame_stride`` into the slot, and one kernel (``mlc_augment_clip``)
+  applies the transform to every frame and writes NCTHW fp32 or channels_last_3d bf16.
+  :func:`augment_clip_reference` is its PyTorch twin.
 """
 from __future__ import annotations
 
@@ -41,7 +48,10 @@ HEADER = struct.Struct('<8s4I2Q24x')
 SEG_MAGIC = b'MLSEG001'
 SEG_HEADER = struct.Struct('<8s4I2Q2I16x')   # ... count, record_bytes, K, kind
 MASK_KINDS = {'planes': 0, 'index': 1}
+CLIP_MAGIC = b'MLVID001'
+CLIP_HEADER = struct.Struct('<8s4I2QI20x')   # ... count, record_bytes, F (frames per record)
 LAYOUTS = {'s2d': 0, 'nhwc8': 1, 'nchw': 2}
+CLIP_LAYOUTS = {'ncthw': 0, 'nthwc': 1}
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
 
@@ -231,6 +241,111 @@ class SegRecordFile:
         return np.asarray(self._m[i, H * W * Cc:]).reshape(H, W, self.planes)
 
 
+def write_clip_records(path: str, clips: Iterable, labels: Iterable[int]) -> int:
+    """Write uint8 ``clips`` ([F, H, W, C] arrays of one shape, or one [N, F, H, W, C] array;
+    F >= 1, C = 1..4) and their int labels to a clip record file; returns the record count.
+    Written to ``path + '.tmp'`` and renamed; the tmp file is removed on error."""
+    tmp = path + '.tmp'
+    n = 0
+    shape = None
+    labs = iter(labels)
+
+    def header(count):
+        F, H, W, Cc = shape
+        return CLIP_HEADER.pack(CLIP_MAGIC, H, W, Cc, 4, count, F * H * W * Cc + 4, F)
+    try:
+        with open(tmp, 'wb') as f:
+            for clip in clips:
+                a = np.ascontiguousarray(clip, dtype=np.uint8)
+                if shape is None:
+                    if a.ndim != 4 or a.shape[0] < 1 or not 1 <= a.shape[3] <= 4:
+                        raise ValueError(f'clip shape {a.shape}: [F, H, W, C] with F >= 1 and C = 1..4')
+                    shape = tuple(int(v) for v in a.shape)
+                    f.write(header(0))
+                if a.shape != shape:
+                    raise ValueError(f'record {n}: shape {a.shape} != {shape}')
+                try:
+                    lab = int(next(labs))
+                except StopIteration:
+                    raise ValueError(f'record {n}: more clips than labels') from None
+                f.write(a.tobytes())
+                f.write(struct.pack('<i', lab))
+                n += 1
+            if n == 0:
+                raise ValueError('no records')
+            f.seek(0)
+            f.write(header(n))
+    except BaseException:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        raise
+    os.replace(tmp, path)
+    return n
+
+
+def pack_clip_frames(video_dirs: Sequence[str], labels: Sequence[int], out: str, frames: int, size: int = 128,
+                     frame_step: int = 1, pad_short: bool = False) -> int:
+    """Pack folders of frame images (one folder per video, files sorted by name) into a clip
+    record file of ``frames`` frames per record.  Frames ``off + i*frame_step`` are taken,
+    the window centred in the folder; each is resized (shorter side to ``size``, bilinear)
+    and centre-cropped to ``size`` x ``size`` as :func:`pack_images` does.  A folder with
+    fewer than ``(frames-1)*frame_step + 1`` frames is an error that names it, unless
+    ``pad_short`` repeats its last frame."""
+    from PIL import Image
+    if frames < 1 or frame_step < 1:
+        raise ValueError(f'frames {frames} / frame_step {frame_step}: both >= 1')
+    if len(video_dirs) != len(labels):
+        raise ValueError(f'{len(video_dirs)} videos but {len(labels)} labels')
+    span = (frames - 1) * frame_step + 1
+
+    def fit(p):
+        im = Image.open(p).convert('RGB')
+        w, h = im.size
+        s = size / min(w, h)
+        im = im.resize((max(size, round(w * s)), max(size, round(h * s))), Image.BILINEAR)
+        w, h = im.size
+        l, t = (w - size) // 2, (h - size) // 2
+        return np.asarray(im.crop((l, t, l + size, t + size)), dtype=np.uint8)
+
+    def gen():
+        for d in video_dirs:
+            files = sorted(os.listdir(d))
+            if not files or (len(files) < span and not pad_short):
+                raise ValueError(f'{d}: {len(files)} frames, {span} needed '
+                                 f'({frames} frames at step {frame_step})')
+            off = max(0, (len(files) - span) // 2)
+            idx = [min(off + i * frame_step, len(files) - 1) for i in range(frames)]
+            yield np.stack([fit(os.path.join(d, files[j])) for j in idx])
+    return write_clip_records(out, gen(), labels)
+
+
+class ClipRecordFile:
+    """numpy view of a clip record file (the python twin of ``mlr_clip_open``)."""
+
+    def __init__(self, path: str):
+        with open(path, 'rb') as f:
+            raw = f.read(CLIP_HEADER.size)
+        if len(raw) < CLIP_HEADER.size:
+            raise ValueError(f'{path}: not a clip record file')
+        magic, H, W, Cc, lb, n, rb, F = CLIP_HEADER.unpack(raw)
+        if magic != CLIP_MAGIC or F < 1 or not 1 <= Cc <= 4 or lb != 4 or rb != F * H * W * Cc + 4:
+            raise ValueError(f'{path}: not a clip record file')
+        self.shape = (H, W, Cc)
+        self.frames = F
+        self.count = n
+        self._m = np.memmap(path, dtype=np.uint8, mode='r', offset=CLIP_HEADER.size, shape=(n, rb))
+
+    def __len__(self):
+        return self.count
+
+    def clip(self, i: int) -> np.ndarray:
+        H, W, Cc = self.shape
+        return np.asarray(self._m[i, :-4]).reshape(self.frames, H, W, Cc)
+
+    def label(self, i: int) -> int:
+        return int(np.asarray(self._m[i, -4:]).view('<i4')[0])
+
+
 # ------------------------------------------------------------------------- runtime
 _RT = None
 
@@ -256,6 +371,10 @@ def runtime():
         'mlr_seg_loader_create': ([vp, i32, i32, i32, i32, f64, f64, f64, f64, u64, i32, i32, i32, i32, i32, i32],
                                   vp),
         'mlr_seg_loader_set_slot': ([vp, i32, vp, vp, vp], i32),
+        'mlr_clip_open': ([C.c_char_p], vp), 'mlr_clip_shape': ([vp, vp], None),
+        'mlr_clip_loader_create': ([vp, i32, i32, i32, i32, i32, i32, f64, f64, f64, f64, u64, i32, i32, i32, i32,
+                                    i32, i32], vp),
+        'mlr_clip_loader_set_slot': ([vp, i32, vp, vp, vp], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -345,6 +464,28 @@ def augment_seg_reference(img: torch.Tensor, mask: torch.Tensor, par: torch.Tens
     return _normalise(torch.stack(outs), mean_istd, layout), m
 
 
+def augment_clip_reference(clips: torch.Tensor, par: torch.Tensor, out_h: int, out_w: int,
+                           mean_istd: Sequence[float], layout: str = 'ncthw') -> torch.Tensor:
+    """PyTorch twin of ``mlc_augment_clip``: clips uint8 [B, T, H, W, C], par int [B, 8]
+    (y0, x0, h, w, flip, t0, frame stride, 0; the last three are not read) -> the normalised
+    clips, logical [B, C, T, oh, ow]: fp32 contiguous for ``ncthw``, bf16 in channels_last_3d
+    storage ([B, T, oh, ow, C] in memory) for ``nthwc``.  Every frame is
+    :func:`augment_reference` with the clip's box, clamped into the image as the kernel
+    clamps it."""
+    if layout not in CLIP_LAYOUTS:
+        raise ValueError(f'clip layout: {" / ".join(CLIP_LAYOUTS)}, not {layout!r}')
+    B, T, H, W, Cc = clips.shape
+    p = par.long()[:, :5].clone()
+    p[:, 0].clamp_(0, H - 1)
+    p[:, 1].clamp_(0, W - 1)
+    p[:, 2] = torch.minimum(p[:, 2].clamp(min=1), H - p[:, 0])
+    p[:, 3] = torch.minimum(p[:, 3].clamp(min=1), W - p[:, 1])
+    x = torch.stack([augment_reference(clips[:, t], p, out_h, out_w, mean_istd, 'nchw') for t in range(T)], dim=2)
+    if layout == 'nthwc':
+        return x.permute(0, 2, 3, 4, 1).contiguous().to(torch.bfloat16).permute(0, 4, 1, 2, 3)
+    return x
+
+
 class RecordLoader:
     """Batches of a record file: dicts {'features', 'targets'} on ``device``.
 
@@ -355,6 +496,7 @@ class RecordLoader:
     ``threads`` host workers, ``depth`` pinned ring slots (>= 3)."""
 
     PAR = 5   # ints per sample in a slot's params
+    LAYOUT_NAMES = LAYOUTS
 
     def __init__(self, path: str, batch_size: int, out_size=224, train: bool = True,
                  scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), seed: int = 0, rank: int = 0, world_size: int = 1,
@@ -373,7 +515,7 @@ class RecordLoader:
         rt = runtime()
         self._rt = rt
         self._open(path)
-        if layout not in LAYOUTS or (layout == 's2d' and (self.C != 3 or self.out_h % 2 or self.out_w % 2)):
+        if layout not in self.LAYOUT_NAMES or (layout == 's2d' and (self.C != 3 or self.out_h % 2 or self.out_w % 2)):
             raise ValueError(f'layout {layout!r} does not fit {self.C}-channel images of {out_size}')
         ms = [0.0] * 8
         for c in range(min(self.C, 4)):
@@ -397,7 +539,7 @@ class RecordLoader:
         B = self.batch_size
         self._slots = []
         for i in range(max(3, int(depth))):
-            img = torch.empty(B, self.H, self.W, self.C, dtype=torch.uint8, pin_memory=pin)
+            img = self._image_buffer(pin_memory=pin)
             lab = self._target_buffer(pin_memory=pin)
             par = torch.empty(B, self.PAR, dtype=torch.int32, pin_memory=pin)
             self._set_slot(self._loader, i, C.c_void_p(img.data_ptr()), C.c_void_p(lab.data_ptr()),
@@ -409,7 +551,7 @@ class RecordLoader:
             self._ms_dev = torch.tensor(ms, dtype=torch.float32, device=self.device)
             self._used = [None, None]   # event: the augment kernel that last read each staging buffer
 
-    # what a segmentation loader does differently (SegRecordLoader)
+    # what a segmentation or clip loader does differently (SegRecordLoader, ClipRecordLoader)
     def _open(self, path):
         rt = self._rt
         self._file = rt.mlr_open(path.encode())
@@ -420,13 +562,15 @@ class RecordLoader:
         self.count, self.H, self.W, self.C = (int(v) for v in shp)
         self._create, self._set_slot = rt.mlr_loader_create, rt.mlr_loader_set_slot
 
+    def _image_buffer(self, **kw):
+        return torch.empty(self.batch_size, self.H, self.W, self.C, dtype=torch.uint8, **kw)
+
     def _target_buffer(self, **kw):
         return torch.empty(self.batch_size, dtype=torch.int64, **kw)
 
     def _staging(self):
-        B = self.batch_size
-        return (torch.empty(B, self.H, self.W, self.C, dtype=torch.uint8, device=self.device),
-                torch.empty(B, self.PAR, dtype=torch.int32, device=self.device))
+        return (self._image_buffer(device=self.device),
+                torch.empty(self.batch_size, self.PAR, dtype=torch.int32, device=self.device))
 
     def _augment_cpu(self, slot):
         img, lab, par = slot
@@ -636,5 +780,86 @@ class SegRecordLoader(RecordLoader):
         return out, self._order(m), done
 
 
+class ClipRecordLoader(RecordLoader):
+    """Batches of a clip record file, on the ring, copy stream and events of
+    :class:`RecordLoader`: ``features`` logical ``[B, C, clip_len, h, w]``, ``targets`` int64
+    ``[B]``.
+
+    A clip is ``clip_len`` frames ``frame_stride`` apart; its span ``(clip_len-1) *
+    frame_stride + 1`` must fit into the file's frames per record.  ``train``: one
+    RandomResizedCrop(scale, ratio) box and one horizontal flip for the whole clip (the draws
+    of :class:`RecordLoader`) and a random first frame; otherwise the centre crop of the
+    centre frames, in file order.  Only the selected frames are copied into the ring and to
+    the device.  ``out_size`` is an int or ``(h, w)``.  ``layout``: ``'ncthw'`` fp32
+    contiguous (the torch engine), ``'nthwc'`` bf16 in channels_last_3d storage (a permuted
+    view of ``[B, T, h, w, C]``, what the generic native engine's 3D sites read)."""
+
+    PAR = 8
+    LAYOUT_NAMES = CLIP_LAYOUTS
+
+    def __init__(self, path: str, batch_size: int, clip_len: int, frame_stride: int = 1, out_size=112,
+                 train: bool = True, scale=(0.3, 1.0), ratio=(3 / 4, 4 / 3), layout: str = 'ncthw', **kw):
+        self.clip_len, self.frame_stride = int(clip_len), int(frame_stride)
+        super().__init__(path, batch_size, out_size=out_size, train=train, scale=scale, ratio=ratio,
+                         layout=layout, **kw)
+
+    def _open(self, path):
+        rt = self._rt
+        self._file = rt.mlr_clip_open(path.encode())
+        if not self._file:
+            raise ValueError(f'{path}: cannot open clip record file')
+        shp = (C.c_uint64 * 5)()
+        rt.mlr_clip_shape(self._file, shp)
+        self.count, self.H, self.W, self.C, self.F = (int(v) for v in shp)
+        T, s = self.clip_len, self.frame_stride
+        if T < 1 or s < 1 or (T - 1) * s + 1 > self.F:
+            raise ValueError(f'{path}: clip_len T={T} at frame_stride s={s} spans {(T - 1) * s + 1} frames, '
+                             f'the records hold F={self.F}')
+        self._create = lambda f, batch, oh, ow, *rest: rt.mlr_clip_loader_create(f, batch, oh, ow, T, s, *rest)
+        self._set_slot = rt.mlr_clip_loader_set_slot
+
+    def _image_buffer(self, **kw):
+        return torch.empty(self.batch_size, self.clip_len, self.H, self.W, self.C, dtype=torch.uint8, **kw)
+
+    def _out_shape(self, B):
+        if self.layout == 'nthwc':
+            return (B, self.clip_len, self.out_h, self.out_w, self.C), torch.bfloat16
+        return (B, self.C, self.clip_len, self.out_h, self.out_w), torch.float32
+
+    def _augment_cpu(self, slot):
+        img, lab, par = slot
+        return augment_clip_reference(img, par, self.out_h, self.out_w, self.mean_istd, self.layout), lab.clone()
+
+    def _augment_gpu(self, k, slot):
+        from mlcomp_amd.ops import _lib
+        img, lab, par = slot
+        dimg, dpar = self._dev[k % 2]
+        cur = torch.cuda.current_stream(self.device)
+        cs = self._copy_stream
+        if self._used[k % 2] is not None:
+            cs.wait_event(self._used[k % 2])
+        with torch.cuda.stream(cs):
+            dimg.copy_(img, non_blocking=True)
+            dpar.copy_(par, non_blocking=True)
+            dlab = lab.to(self.device, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(cs)
+        cur.wait_event(done)
+        dlab.record_stream(cur)
+        shape, dt = self._out_shape(self.batch_size)
+        out = torch.empty(shape, dtype=dt, device=self.device)
+        _lib.call('mlc_augment_clip', _lib.ptr(dimg), _lib.ptr(dpar), _lib.ptr(self._ms_dev), _lib.ptr(out),
+                  self.batch_size, self.clip_len, self.H, self.W, self.C, self.out_h, self.out_w,
+                  CLIP_LAYOUTS[self.layout], _lib.stream())
+        used = torch.cuda.Event()
+        used.record(cur)
+        self._used[k % 2] = used
+        if self.layout == 'nthwc':
+            out = out.permute(0, 4, 1, 2, 3)
+        return out, dlab, done
+
+
 __all__ = ['write_records', 'pack_images', 'RecordFile', 'RecordLoader', 'augment_reference', 'runtime',
-           'write_seg_records', 'pack_seg_images', 'SegRecordFile', 'SegRecordLoader', 'augment_seg_reference']
+           'write_seg_records', 'pack_seg_images', 'SegRecordFile', 'SegRecordLoader', 'augment_seg_reference',
+           'write_clip_records', 'pack_clip_frames', 'ClipRecordFile', 'ClipRecordLoader', 'augment_clip_reference',
+           'CLIP_LAYOUTS']

@@ -345,14 +345,17 @@ class Runner:
         """``dataset: records``: the native input pipeline over ``path`` (train) and
         ``valid_path`` record files (:mod:`mlcomp_amd.train.records`); the native engine
         gets the stem's space-to-depth image straight from the augment kernel."""
-        from .records import SEG_MAGIC, RecordLoader
+        from .records import CLIP_MAGIC, SEG_MAGIC, RecordLoader
         try:
             with open(dp['path'], 'rb') as f:
-                seg_file = f.read(8) == SEG_MAGIC
+                magic = f.read(8)
         except OSError:     # the loader below reports a file it cannot open
-            seg_file = False
-        if dp.get('kind', 'segmentation' if seg_file else 'classification') == 'segmentation':
+            magic = b''
+        kind = dp.get('kind', {SEG_MAGIC: 'segmentation', CLIP_MAGIC: 'video'}.get(magic, 'classification'))
+        if kind == 'segmentation':
             return self._seg_record_loaders(dp, bs)
+        if kind == 'video':
+            return self._clip_record_loaders(dp, bs)
         layout = 's2d' if self.state.native and self.native_kind == 'resnet' else 'nchw'
         common = dict(out_size=int(dp.get('image_size', 224)), rank=self.rank, world_size=self.world_size,
                       threads=int(dp.get('num_workers', 8) or 8), layout=layout, device=self.device,
@@ -387,6 +390,27 @@ class Runner:
                                        mask_order='pixel' if native else 'nkhw', **common)
         if dp.get('valid_path'):
             out['valid'] = SegRecordLoader(dp['valid_path'], bs, train=False, **common)
+        return out
+
+    def _clip_record_loaders(self, dp, bs) -> 'OrderedDict[str, object]':
+        """``dataset: records`` over clip files (``kind: video``, or told from the file
+        header): clips of ``clip_length`` frames ``frame_stride`` apart, one crop box and flip
+        per clip.  A stage on the generic native engine on a GPU gets bf16 channels_last_3d
+        clips, what its 3D sites read without a layout pass; every other stage gets NCTHW
+        fp32."""
+        from .records import ClipRecordLoader
+        native = self.state.native and self.native_kind == 'generic' and self.device.type == 'cuda'
+        size = dp.get('image_size', 112)
+        size = tuple(int(v) for v in size) if isinstance(size, (list, tuple)) else int(size)
+        common = dict(clip_len=int(dp.get('clip_length', 8)), frame_stride=int(dp.get('frame_stride', 1)),
+                      out_size=size, rank=self.rank, world_size=self.world_size,
+                      threads=int(dp.get('num_workers', 8) or 8), layout='nthwc' if native else 'ncthw',
+                      device=self.device, seed=int(dp.get('seed', 0)))
+        out = OrderedDict()
+        out['train'] = ClipRecordLoader(dp['path'], bs, train=True, scale=tuple(dp.get('scale', (0.3, 1.0))),
+                                        ratio=tuple(dp.get('ratio', (3 / 4, 4 / 3))), **common)
+        if dp.get('valid_path'):
+            out['valid'] = ClipRecordLoader(dp['valid_path'], bs, train=False, **common)
         return out
 
     def _seg_stem_s2d(self) -> bool:
