@@ -146,7 +146,10 @@ class GraphedStep:
             self._body()
             return
         if self.graph is None:
-            if self.calls <= self.warmup_eager:
+            # a damped FusedSGD's first step differs from the later ones in a kernel argument
+            # (it seeds momentum = d): it stays eager even with warmup_eager == 0 (inference
+            # steps have no optimizer)
+            if self.calls <= self.warmup_eager or getattr(getattr(self, 'opt', None), 'seeds_momentum', False):
                 s = torch.cuda.Stream(self.device)
                 s.wait_stream(torch.cuda.current_stream(self.device))
                 with torch.cuda.stream(s):

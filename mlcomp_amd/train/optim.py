@@ -71,10 +71,29 @@ class FusedSGD(_ArenaStateMixin):
         """Host side of one step (call once per step, outside any graph)."""
         self.steps += 1
 
+    @property
+    def seeds_momentum(self):
+        """True while the coming ``step()`` is the one that seeds momentum = d (``first``).
+
+        torch.optim.SGD's first step stores d itself, not (1-dampening)*d.  With zeroed
+        buffers "mu*0 + (1-dampening)*d" equals that only when dampening == 0, so only a
+        damped run needs the kernel's ``first`` flag, and only on step 1 as ``prepare()``
+        counts it (a run resumed by ``load_state_dict`` with steps > 0 never seeds).  A
+        captured graph replays with frozen kernel arguments, so this one step must run
+        eagerly: :class:`~mlcomp_amd.train.graphed.GraphedStep` keeps it out of the capture
+        and ``step()`` refuses to be captured while it holds.  With dampening == 0 the
+        arguments are the same on every step."""
+        return self.steps == 1 and self.momentum != 0 and self.dampening != 0
+
+    def _first(self):
+        first = self.seeds_momentum
+        if first and self.arena.device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('FusedSGD with dampening != 0: the first step seeds the momentum buffers and '
+                               'cannot be captured into a graph; run it eagerly')
+        return first
+
     def step(self):
-        # the first step seeds momentum = grad (torch.optim.SGD semantics); with zeroed
-        # buffers "mu*0 + (1-dampening)*g" equals that when dampening == 0, which keeps
-        # the kernel arguments identical across steps (HIP-graph friendly).
+        first = self._first()
         for a in self.arena.arenas():
             segs = a.segments()
             if segs != [(0, a.numel)]:       # frozen slots: update the live ranges only
@@ -83,13 +102,13 @@ class FusedSGD(_ArenaStateMixin):
                 continue
             Fn.sgd_step(a.master, a.grad, a.state['momentum'], a.mirror, self.hyper,
                         a.numel if (a.decay or self.decay_all) else 0, a.numel if a.mirror is not None else 0,
-                        self.momentum, self.dampening, self.wd, self.nesterov, False)
+                        self.momentum, self.dampening, self.wd, self.nesterov, first)
 
     def step_slice(self, a, start, end):
         """The update of elements [start, end) of arena ``a`` (one gradient bucket)."""
         p, g, bf, n, nd, nb = self._slice(a, start, end)
         Fn.sgd_step(p, g, a.state['momentum'][start:end], bf, self.hyper, nd, nb, self.momentum, self.dampening,
-                    self.wd, self.nesterov, False)
+                    self.wd, self.nesterov, self._first())
 
 
 class FusedAdam(_ArenaStateMixin):
