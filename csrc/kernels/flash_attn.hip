@@ -24,6 +24,13 @@
 // -inf before the running max (forward) or in the exponent (backward), so their
 // probabilities are exactly 0 whatever the saved log-sum-exp.
 //
+// Packed variable-length batches (the *_varlen entry points; mode bit M_VARLEN of the same
+// three streaming kernels): sequences lie back to back in a [T]-row buffer and block (b, h, blk)
+// reads its sequence's first row and length from cu_seqlens in device memory.  The grid is sized
+// from nseq_max, H and ceil(max_len / 128); a block whose 128 rows start at or past the length
+// returns before any barrier or LDS traffic, and no key / query tile past the length is
+// fetched.  Dropout keeps the padded layout's element index at S = max_len.
+//
 // Work split (one 256-thread block = 4 waves x 32 rows, blocks XCD-remapped so the blocks
 // sharing one (b, h) K/V slice sit on one XCD's L2):
 // * forward: a wave owns 32 queries; scores are computed transposed, S^T = K Q^T
@@ -140,6 +147,7 @@ struct Tile {
 // Mask modes (a template parameter of the streaming kernels; 0 is the unmasked code).
 constexpr int M_CAUSAL = 1;   // top-left aligned: query q sees keys <= q
 constexpr int M_BIAS = 2;     // additive fp32 bias[b * sb + h * sh + q * S + key], finite or -inf
+constexpr int M_VARLEN = 4;   // packed sequences: rows and length of slot b from cu_seqlens (no bias operands)
 struct AttnBias {
   const float* p;
   long sb, sh;   // batch / head strides in elements (0 broadcasts)
@@ -161,6 +169,36 @@ __device__ __forceinline__ void load_bias_keys(f32x4 (&bv)[2][4], const float* r
         for (int e = 0; e < 4; ++e) bv[i][g][e] = row[min(key + e, S - 1)];
       }
     }
+}
+
+// Packed variable-length batches (the *_varlen entry points): sequence b owns rows
+// cu[b] .. cu[b+1]-1 of the [T]-row buffers; the kernels' S is then max_len (the grid's and the
+// dropout index's sequence length) and lse / dot are [H][T].
+struct VarLen {
+  const int* cu;   // int32 [nseq_max + 1], device memory
+  int T;
+};
+// rows of one (sequence, head): first row, length, and base of its lse / dot entries
+struct Seq {
+  long row0, stat0;
+  int len;
+};
+template <bool VARLEN>
+__device__ __forceinline__ Seq seq_of(int b, int hd, int bh, int S, const VarLen& vl) {
+  Seq s;
+  if constexpr (VARLEN) {
+    // cu_seqlens is device memory nobody has checked since the host did: clamp the start into
+    // [0, T] and the length to max_len and to the rows left, so no index leaves the buffers
+    const int c0 = min(max(vl.cu[b], 0), vl.T);
+    s.len = min(min(vl.cu[b + 1] - c0, S), vl.T - c0);
+    s.row0 = c0;
+    s.stat0 = (long)hd * vl.T + c0;
+  } else {
+    s.len = S;
+    s.row0 = (long)b * S;
+    s.stat0 = (long)bh * S;
+  }
+  return s;
 }
 
 struct Geo {
@@ -196,18 +234,21 @@ template <int D, bool DROP, int MASK>
 __global__ void __launch_bounds__(NT)
 fwd_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, bf16* __restrict__ out,
            float* __restrict__ lse, int S, int H, int nqb, float sl2, uint32_t thr, float inv_keep,
-           const uint32_t* __restrict__ seedp, uint32_t salt, AttnBias ab) {
+           const uint32_t* __restrict__ seedp, uint32_t salt, AttnBias ab, VarLen vl) {
   constexpr int NS = D / 16, NJ = D / 32, IMG = KT * D * 2, BUF = 2 * IMG + KT * 4;
-  constexpr bool CAUSAL = (MASK & M_CAUSAL) != 0, BIAS = (MASK & M_BIAS) != 0;
+  constexpr bool CAUSAL = (MASK & M_CAUSAL) != 0, BIAS = (MASK & M_BIAS) != 0, VARLEN = (MASK & M_VARLEN) != 0;
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];   // [buffer][K | V | key bias * log2e]
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, hh = lane >> 5, l32 = lane & 31;
   const Geo G = CAUSAL ? geo_heavy_first(H, nqb, true) : geo(H, nqb);
   const int E = H * D, ld = 3 * E;
-  const bf16* Qg = qkv + (size_t)G.b * S * ld + G.hd * D;
+  const Seq sq = seq_of<VARLEN>(G.b, G.hd, G.bh, S, vl);
+  const int L = sq.len;   // this sequence's length (S itself unless packed)
+  if (VARLEN && G.blk * 128 >= L) return;   // a grid slot past the sequence (or an empty slot): block-uniform
+  const bf16* Qg = qkv + (size_t)sq.row0 * ld + G.hd * D;
   const bf16* Kg = Qg + E;
   const bf16* Vg = Qg + 2 * E;
   const int q = G.blk * 128 + 32 * w + l32;
-  const int qc = min(q, S - 1);
+  const int qc = min(q, L - 1);
   bf16x8 qf[NS];
 #pragma unroll
   for (int s = 0; s < NS; ++s) qf[s] = gfrag(Qg, ld, qc, s, lane);
@@ -221,7 +262,7 @@ fwd_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, bf1
   Tile<D> tk, tv;
   float kbv = 0.f;
   auto fetch = [&](int t) {
-    const int valid = min(KT, S - t * KT);
+    const int valid = min(KT, L - t * KT);
     tk.load(Kg + (size_t)t * KT * ld, ld, tid, valid);
     tv.load(Vg + (size_t)t * KT * ld, ld, tid, valid);
     if (tid < KT) kbv = tid >= valid ? -INFINITY : kb ? kb[t * KT + tid] * LOG2E : 0.f;
@@ -236,7 +277,7 @@ fwd_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, bf1
   put(0);
   __syncthreads();
   // a partial last tile is masked; a causal query block stops at the tile of its last query
-  const int nt = CAUSAL ? min((S + KT - 1) / KT, 2 * G.blk + 2) : (S + KT - 1) / KT;
+  const int nt = CAUSAL ? min((L + KT - 1) / KT, 2 * G.blk + 2) : (L + KT - 1) / KT;
   const float* brow = BIAS ? ab.p + G.b * ab.sb + G.hd * ab.sh + (size_t)qc * S : nullptr;
   const int wq_last = G.blk * 128 + 32 * __builtin_amdgcn_readfirstlane(w) + 31;   // this wave's last query
   for (int t = 0; t < nt; ++t) {
@@ -318,9 +359,9 @@ fwd_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, bf1
   for (int j = 0; j < NJ; ++j)
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[j][r] *= inv;
-  if (q < S) {
-    if (hh == 0) lse[(size_t)G.bh * S + q] = l > 0.f ? (m + __log2f(l)) * LN2 : INFINITY;
-    store_rows<NJ>(out + ((size_t)G.b * S + q) * E + G.hd * D, o, lane);
+  if (q < L) {
+    if (hh == 0) lse[sq.stat0 + q] = l > 0.f ? (m + __log2f(l)) * LN2 : INFINITY;
+    store_rows<NJ>(out + ((size_t)sq.row0 + q) * E + G.hd * D, o, lane);
   }
 }
 
@@ -330,20 +371,23 @@ __global__ void __launch_bounds__(NT)
 dq_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, const bf16* __restrict__ out,
           const bf16* __restrict__ dout, const float* __restrict__ lse, float* __restrict__ dot,
           bf16* __restrict__ dqkv, int S, int H, int nqb, float scale, float sl2, uint32_t thr, float inv_keep,
-          const uint32_t* __restrict__ seedp, uint32_t salt, AttnBias ab) {
+          const uint32_t* __restrict__ seedp, uint32_t salt, AttnBias ab, VarLen vl) {
   constexpr int NS = D / 16, NJ = D / 32, IMG = KT * D * 2, BUF = 2 * IMG + KT * 4;
-  constexpr bool CAUSAL = (MASK & M_CAUSAL) != 0, BIAS = (MASK & M_BIAS) != 0;
+  constexpr bool CAUSAL = (MASK & M_CAUSAL) != 0, BIAS = (MASK & M_BIAS) != 0, VARLEN = (MASK & M_VARLEN) != 0;
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];   // [buffer][K | V | key bias * log2e]
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, hh = lane >> 5, l32 = lane & 31;
   const Geo G = CAUSAL ? geo_heavy_first(H, nqb, true) : geo(H, nqb);
   const int E = H * D, ld = 3 * E;
-  const bf16* Qg = qkv + (size_t)G.b * S * ld + G.hd * D;
+  const Seq sq = seq_of<VARLEN>(G.b, G.hd, G.bh, S, vl);
+  const int L = sq.len;
+  if (VARLEN && G.blk * 128 >= L) return;   // as in fwd_kernel
+  const bf16* Qg = qkv + (size_t)sq.row0 * ld + G.hd * D;
   const bf16* Kg = Qg + E;
   const bf16* Vg = Qg + 2 * E;
-  const bf16* Og = out + (size_t)G.b * S * E + G.hd * D;
-  const bf16* dOg = dout + (size_t)G.b * S * E + G.hd * D;
+  const bf16* Og = out + (size_t)sq.row0 * E + G.hd * D;
+  const bf16* dOg = dout + (size_t)sq.row0 * E + G.hd * D;
   const int q = G.blk * 128 + 32 * w + l32;
-  const int qc = min(q, S - 1);
+  const int qc = min(q, L - 1);
   bf16x8 qf[NS], of[NS];
   float dt = 0.f;
 #pragma unroll
@@ -355,8 +399,8 @@ dq_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, cons
     for (int e = 0; e < 8; ++e) dt += (float)of[s][e] * (float)ov[e];
   }
   dt += __shfl_xor(dt, 32, 64);
-  if (q < S && hh == 0) dot[(size_t)G.bh * S + q] = dt;
-  const float l2 = lse[(size_t)G.bh * S + qc] * LOG2E;
+  if (q < L && hh == 0) dot[sq.stat0 + q] = dt;
+  const float l2 = lse[sq.stat0 + qc] * LOG2E;
   const float* kb = key_bias ? key_bias + (size_t)G.b * S : nullptr;
   const uint32_t seed = seedp ? *seedp : 0u;
   const uint32_t rowidx = ((uint32_t)G.bh * S + qc) * S;
@@ -366,7 +410,7 @@ dq_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, cons
   Tile<D> tk, tv;
   float kbv = 0.f;
   auto fetch = [&](int t) {
-    const int valid = min(KT, S - t * KT);
+    const int valid = min(KT, L - t * KT);
     tk.load(Kg + (size_t)t * KT * ld, ld, tid, valid);
     tv.load(Vg + (size_t)t * KT * ld, ld, tid, valid);
     if (tid < KT) kbv = tid >= valid ? -INFINITY : kb ? kb[t * KT + tid] * LOG2E : 0.f;
@@ -381,7 +425,7 @@ dq_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, cons
   put(0);
   __syncthreads();
   // a partial last tile is masked; a causal query block stops at the tile of its last query
-  const int nt = CAUSAL ? min((S + KT - 1) / KT, 2 * G.blk + 2) : (S + KT - 1) / KT;
+  const int nt = CAUSAL ? min((L + KT - 1) / KT, 2 * G.blk + 2) : (L + KT - 1) / KT;
   const float* brow = BIAS ? ab.p + G.b * ab.sb + G.hd * ab.sh + (size_t)qc * S : nullptr;
   const int wq_last = G.blk * 128 + 32 * __builtin_amdgcn_readfirstlane(w) + 31;   // this wave's last query
   for (int t = 0; t < nt; ++t) {
@@ -434,7 +478,7 @@ dq_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, cons
     if (t + 1 < nt) put(t + 1);
     __syncthreads();
   }
-  if (q < S) store_rows<NJ>(dqkv + ((size_t)G.b * S + q) * ld + G.hd * D, dq, lane);
+  if (q < L) store_rows<NJ>(dqkv + ((size_t)sq.row0 + q) * ld + G.hd * D, dq, lane);
 }
 
 // ------------------------------------------------------------------ backward: dK, dV
@@ -443,22 +487,25 @@ __global__ void __launch_bounds__(NT)
 dkv_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, const bf16* __restrict__ dout,
            const float* __restrict__ lse, const float* __restrict__ dot, bf16* __restrict__ dqkv, int S, int H,
            int nkb, float scale, float sl2, uint32_t thr, float inv_keep, const uint32_t* __restrict__ seedp,
-           uint32_t salt, AttnBias ab) {
+           uint32_t salt, AttnBias ab, VarLen vl) {
   constexpr int NS = D / 16, NJ = D / 32, IMG = KT * D * 2, BUF = 2 * IMG + 2 * KT * 4;
-  constexpr bool CAUSAL = (MASK & M_CAUSAL) != 0, BIAS = (MASK & M_BIAS) != 0;
+  constexpr bool CAUSAL = (MASK & M_CAUSAL) != 0, BIAS = (MASK & M_BIAS) != 0, VARLEN = (MASK & M_VARLEN) != 0;
   // [buffer][Q image | dO image | lse*log2e [64] | dot [64]]
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, hh = lane >> 5, l32 = lane & 31;
   const Geo G = CAUSAL ? geo_heavy_first(H, nkb, false) : geo(H, nkb);
   const int E = H * D, ld = 3 * E;
-  const bf16* Qg = qkv + (size_t)G.b * S * ld + G.hd * D;
+  const Seq sq = seq_of<VARLEN>(G.b, G.hd, G.bh, S, vl);
+  const int L = sq.len;
+  if (VARLEN && G.blk * 128 >= L) return;   // as in fwd_kernel
+  const bf16* Qg = qkv + (size_t)sq.row0 * ld + G.hd * D;
   const bf16* Kg = Qg + E;
   const bf16* Vg = Qg + 2 * E;
-  const bf16* dOg = dout + (size_t)G.b * S * E + G.hd * D;
-  const float* Lg = lse + (size_t)G.bh * S;
-  const float* Dg = dot + (size_t)G.bh * S;
+  const bf16* dOg = dout + (size_t)sq.row0 * E + G.hd * D;
+  const float* Lg = lse + sq.stat0;
+  const float* Dg = dot + sq.stat0;
   const int key = G.blk * 128 + 32 * w + l32;
-  const int kc = min(key, S - 1);
+  const int kc = min(key, L - 1);
   bf16x8 kf[NS], vf[NS];
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
@@ -476,7 +523,7 @@ dkv_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, con
   Tile<D> tq, to;
   float ld_v = 0.f;   // this thread's lse / dot element of the next tile (threads 0..127)
   auto fetch = [&](int t) {
-    const int valid = min(KT, S - t * KT);
+    const int valid = min(KT, L - t * KT);
     tq.load(Qg + (size_t)t * KT * ld, ld, tid, valid);
     to.load(dOg + (size_t)t * KT * E, E, tid, valid);
     // queries past S: lse = +inf makes their probabilities exactly 0
@@ -489,13 +536,13 @@ dkv_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, con
     to.store(bp + IMG, tid);
     if (tid < 2 * KT) reinterpret_cast<float*>(bp + 2 * IMG)[tid] = ld_v;
   };
-  // causal: the first query tile that sees this key block (128 * blk < S, so t0 < nt); the
+  // causal: the first query tile that sees this key block (128 * blk < L, so t0 < nt); the
   // staging buffers alternate on the tile's parity, whichever tile comes first
   const int t0 = CAUSAL ? 2 * G.blk : 0;
   fetch(t0);
   put(t0);
   __syncthreads();
-  const int nt = (S + KT - 1) / KT;   // a partial last tile is masked
+  const int nt = (L + KT - 1) / KT;   // a partial last tile is masked
   const float* bcol = BIAS ? ab.p + G.b * ab.sb + G.hd * ab.sh + kc : nullptr;
   const int wk_first = G.blk * 128 + 32 * __builtin_amdgcn_readfirstlane(w);   // this wave's first key
   for (int t = t0; t < nt; ++t) {
@@ -532,7 +579,7 @@ dkv_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, con
           const int r = 4 * g + e;
           float x = sc[i][r] * sl2 + kbl;
           // padded queries of a tail tile re-read the last row (their lse = +inf zeroes them)
-          if constexpr (BIAS) x += bcol[(size_t)min(t * KT + q0 + e, S - 1) * S] * LOG2E;
+          if constexpr (BIAS) x += bcol[(size_t)min(t * KT + q0 + e, L - 1) * S] * LOG2E;
           if constexpr (CAUSAL)
             if (diag && t * KT + q0 + e < key) x = -INFINITY;   // p exactly 0
           const float p = __builtin_amdgcn_exp2f(x - L4[e]);
@@ -562,8 +609,8 @@ dkv_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, con
     if (t + 1 < nt) put(t + 1);
     __syncthreads();
   }
-  if (key < S) {
-    bf16* dst = dqkv + ((size_t)G.b * S + key) * ld + G.hd * D;
+  if (key < L) {
+    bf16* dst = dqkv + ((size_t)sq.row0 + key) * ld + G.hd * D;
     store_rows<NJ>(dst + E, dk, lane);
     store_rows<NJ>(dst + 2 * E, dv, lane);
   }
@@ -896,12 +943,67 @@ int flash_fwd(const bf16* qkv, const float* key_bias, bf16* out, float* lse, int
   const int nqb = (S + 127) / 128;
   const dim3 grid(B * H * nqb);
   const AttnBias ab = bias_arg(attn_bias, stride_b, stride_h, S);
+  const VarLen vl{nullptr, 0};
 #define FWD(DD, DR, MM) hipLaunchKernelGGL((fwd_kernel<DD, DR, MM>), grid, dim3(NT), 0, st, qkv, key_bias, out, lse, S, \
-                                           H, nqb, scale * LOG2E, t, k, seed, salt, ab)
+                                           H, nqb, scale * LOG2E, t, k, seed, salt, ab, vl)
   FLASH_DISPATCH(FWD);
 #undef FWD
   return hipGetLastError();
 }
+
+// instantiate X(D, DROP, MASK) of the packed form: M_VARLEN with or without M_CAUSAL
+#define VARLEN_DISPATCH(X)                                                                            \
+  do {                                                                                                \
+    if (D == 64) { if (t) { VARLEN_MASKS(X, 64, true) } else { VARLEN_MASKS(X, 64, false) } }         \
+    else { if (t) { VARLEN_MASKS(X, 128, true) } else { VARLEN_MASKS(X, 128, false) } }               \
+  } while (0)
+#define VARLEN_MASKS(X, DD, DR) \
+  if (causal) X(DD, DR, M_VARLEN | M_CAUSAL); else X(DD, DR, M_VARLEN);
+
+// the packed calls' shape rule: T rows, nseq slots of at most max_len rows each
+bool varlen_shape_ok(const int* cu, int T, int nseq, int max_len, int H, int D) {
+  return cu && T > 0 && nseq > 0 && max_len >= 1 && H > 0 && (D == 64 || D == 128);
+}
+
+int flash_fwd_varlen(const bf16* qkv, const int* cu, bf16* out, float* lse, int T, int nseq, int max_len, int H, int D,
+                     float scale, float p, const uint32_t* seed, uint32_t salt, int causal, hipStream_t st) {
+  if (!varlen_shape_ok(cu, T, nseq, max_len, H, D)) return -1;
+  const uint32_t t = p > 0.f ? drop_threshold(p) : 0u;
+  const float k = p > 0.f ? 1.f / (1.f - p) : 1.f;
+  const int nqb = (max_len + 127) / 128;
+  const dim3 grid(nseq * H * nqb);   // from nseq_max, H and max_len only: fixed under graph replay
+  const AttnBias ab = bias_arg(nullptr, 0, 0, max_len);
+  const VarLen vl{cu, T};
+#define FWD(DD, DR, MM) hipLaunchKernelGGL((fwd_kernel<DD, DR, MM>), grid, dim3(NT), 0, st, qkv, nullptr, out, lse, \
+                                           max_len, H, nqb, scale * LOG2E, t, k, seed, salt, ab, vl)
+  VARLEN_DISPATCH(FWD);
+#undef FWD
+  return hipGetLastError();
+}
+
+int flash_bwd_varlen(const bf16* qkv, const int* cu, const bf16* out, const bf16* dout, const float* lse, float* dot,
+                     bf16* dqkv, int T, int nseq, int max_len, int H, int D, float scale, float p,
+                     const uint32_t* seed, uint32_t salt, int causal, hipStream_t st) {
+  if (!varlen_shape_ok(cu, T, nseq, max_len, H, D)) return -1;
+  const uint32_t t = p > 0.f ? drop_threshold(p) : 0u;
+  const float k = p > 0.f ? 1.f / (1.f - p) : 1.f;
+  const int nb = (max_len + 127) / 128;
+  const dim3 grid(nseq * H * nb);
+  const AttnBias ab = bias_arg(nullptr, 0, 0, max_len);
+  const VarLen vl{cu, T};
+#define BWD(DD, DR, MM)                                                                                             \
+  do {                                                                                                              \
+    hipLaunchKernelGGL((dq_kernel<DD, DR, MM>), grid, dim3(NT), 0, st, qkv, nullptr, out, dout, lse, dot, dqkv,     \
+                       max_len, H, nb, scale, scale * LOG2E, t, k, seed, salt, ab, vl);                            \
+    hipLaunchKernelGGL((dkv_kernel<DD, DR, MM>), grid, dim3(NT), 0, st, qkv, nullptr, dout, lse, dot, dqkv,         \
+                       max_len, H, nb, scale, scale * LOG2E, t, k, seed, salt, ab, vl);                            \
+  } while (0)
+  VARLEN_DISPATCH(BWD);
+#undef BWD
+  return hipGetLastError();
+}
+#undef VARLEN_MASKS
+#undef VARLEN_DISPATCH
 
 int flash_bwd(const bf16* qkv, const float* key_bias, const bf16* out, const bf16* dout, const float* lse, float* dot,
               bf16* dqkv, int B, int S, int H, int D, float scale, float p, const uint32_t* seed, uint32_t salt,
@@ -924,12 +1026,13 @@ int flash_bwd(const bf16* qkv, const float* key_bias, const bf16* out, const bf1
   const int nb = (S + 127) / 128;
   const dim3 grid(B * H * nb);
   const AttnBias ab = bias_arg(attn_bias, stride_b, stride_h, S);
+  const VarLen vl{nullptr, 0};
 #define BWD(DD, DR, MM)                                                                                              \
   do {                                                                                                               \
     hipLaunchKernelGGL((dq_kernel<DD, DR, MM>), grid, dim3(NT), 0, st, qkv, key_bias, out, dout, lse, dot, dqkv, S, H, \
-                       nb, scale, scale * LOG2E, t, k, seed, salt, ab);                                              \
+                       nb, scale, scale * LOG2E, t, k, seed, salt, ab, vl);                                          \
     hipLaunchKernelGGL((dkv_kernel<DD, DR, MM>), grid, dim3(NT), 0, st, qkv, key_bias, dout, lse, dot, dqkv, S, H, nb, \
-                       scale, scale * LOG2E, t, k, seed, salt, ab);                                                  \
+                       scale, scale * LOG2E, t, k, seed, salt, ab, vl);                                              \
   } while (0)
   FLASH_DISPATCH(BWD);
 #undef BWD
@@ -975,6 +1078,29 @@ MLC_EXPORT int mlc_flash_bwd_masked(const bf16* qkv, const float* key_bias, cons
                                     const float* attn_bias, long stride_b, long stride_h, hipStream_t st) {
   return flash_bwd(qkv, key_bias, out, dout, lse, dot, dqkv, B, S, H, D, scale, p, seed, salt, causal, attn_bias,
                    stride_b, stride_h, st);
+}
+
+// Packed variable-length batches: qkv [T][3*H*D], out / dout [T][H*D], lse / dot fp32 [H][T]
+// (index h*T + row).  cu_seqlens int32 [nseq_max + 1] in device memory, non-decreasing,
+// cu[0] = 0, cu[nseq_max] <= T: sequence b owns rows cu[b] .. cu[b+1]-1 (none: an empty slot);
+// max_len bounds every length.  The grid depends on nseq_max, H and max_len only, and every
+// length is read (and clamped to max_len and to the rows left) on the device, so a captured
+// graph replays on another split.  Rows of no sequence are not written: the caller passes
+// zero-filled out / lse / dqkv.  Dropout drops element ((b*H + h)*max_len + q)*max_len + key
+// (q, key within the sequence), what the padded call at S = max_len drops.  causal != 0 as in
+// the masked entry points; no bias operands.
+MLC_EXPORT int mlc_flash_fwd_varlen(const bf16* qkv, const int* cu_seqlens, bf16* out, float* lse, int T,
+                                    int nseq_max, int max_len, int H, int D, float scale, float p,
+                                    const uint32_t* seed, uint32_t salt, int causal, hipStream_t st) {
+  return flash_fwd_varlen(qkv, cu_seqlens, out, lse, T, nseq_max, max_len, H, D, scale, p, seed, salt, causal, st);
+}
+
+MLC_EXPORT int mlc_flash_bwd_varlen(const bf16* qkv, const int* cu_seqlens, const bf16* out, const bf16* dout,
+                                    const float* lse, float* dot, bf16* dqkv, int T, int nseq_max, int max_len,
+                                    int H, int D, float scale, float p, const uint32_t* seed, uint32_t salt,
+                                    int causal, hipStream_t st) {
+  return flash_bwd_varlen(qkv, cu_seqlens, out, dout, lse, dot, dqkv, T, nseq_max, max_len, H, D, scale, p, seed,
+                          salt, causal, st);
 }
 
 // A/B knob of the S = 128 fused backward: value 0 / 1 sets it, < 0 only reads; returns the

@@ -9,6 +9,12 @@ for head dim 64 with S in {64, 128}, streaming flash kernels for head dim 64 / 1
 S that is a multiple of 64); other shapes fall back to library batched GEMMs around the
 softmax kernel.
 
+Packed mode (``NativeBert(..., packed_tokens=T)``) lays whole sequences back to back in ``T``
+rows and runs the varlen attention kernels over ``cu_seqlens``; the dense GEMMs, LayerNorms,
+dropout and weight gradients are the same calls on ``T`` rows.  Only the attention, the
+position embedding (a gather through ``pos_ids``), the [CLS] gather / scatter (rows ``cu[b]``)
+and the loss mean (over the real sequences) know where sequences begin.
+
 Parameters live in the flat arenas (``ops.arena``): matmul weights and embedding tables
 in the decay arena (bf16 mirror for the kernels), biases and LayerNorm affine in the
 no-decay arena - so AdamW is one fused launch per arena and the RCCL bucketer all-reduces
@@ -21,7 +27,7 @@ captured HIP graph draws fresh masks every replay and backward regenerates them.
 from __future__ import annotations
 
 import math
-from typing import List
+from typing import List, Optional
 
 import os
 
@@ -198,8 +204,12 @@ class NativeBertLayer:
         qkv, _ = self.qkv.fwd(x)
         # fused attention (any S, head dim <= 128): reads q/k/v in place, writes the
         # merged-head context
-        ctx2, lse = Tx.attn_fwd(qkv, key_bias, B, S, nh, 1.0 / math.sqrt(dh), pa, net.seed, self.salt,
-                                head_dim=dh)
+        if net.packed:   # sequences back to back, delimited by the device-resident cu_seqlens
+            ctx2, lse = Tx.attn_fwd_varlen(qkv, net.cu, S, nh, 1.0 / math.sqrt(dh), pa, net.seed, self.salt,
+                                           head_dim=dh)
+        else:
+            ctx2, lse = Tx.attn_fwd(qkv, key_bias, B, S, nh, 1.0 / math.sqrt(dh), pa, net.seed, self.salt,
+                                    head_dim=dh)
         att = (qkv, lse)
         ao, _ = self.out.fwd(ctx2)
         h1, s1, m1, r1 = Tx.ln_fwd(x, ao, self.ln1.g.master, self.ln1.b.master, net.c.eps, p_in=ph,
@@ -223,8 +233,12 @@ class NativeBertLayer:
         ds1, dao = self.ln1.bwd(dh1, s1, m1, r1, p_in=ph, seed=net.seed, salt_in=self.salt + 1, want_dr=True)
         dctx2 = self.out.backward(dao, ctx2)
         qkv, lse = att
-        dqkv = Tx.attn_bwd(qkv, key_bias, dctx2, lse, B, S, nh, 1.0 / math.sqrt(dh), pa, net.seed, self.salt,
-                           head_dim=dh, ctx=ctx2)
+        if net.packed:
+            dqkv = Tx.attn_bwd_varlen(qkv, net.cu, S, dctx2, lse, nh, 1.0 / math.sqrt(dh), pa, net.seed, self.salt,
+                                      head_dim=dh, ctx=ctx2)
+        else:
+            dqkv = Tx.attn_bwd(qkv, key_bias, dctx2, lse, B, S, nh, 1.0 / math.sqrt(dh), pa, net.seed, self.salt,
+                               head_dim=dh, ctx=ctx2)
         return self.qkv.backward(dqkv, x, addend=ds1)
 
 
@@ -245,9 +259,7 @@ class _BertLayerFn(torch.autograd.Function):
 class _EmbedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ids, tt, anchor, net: 'NativeBert'):
-        B, S = ids.shape
-        e = (net.word.bf16[ids].float() + net.pos.bf16[:S][None].float() + net.tok_type.bf16[tt].float())
-        e = e.to(torch.bfloat16).view(B * S, -1)
+        e = net.embed(ids, tt)
         y, s, m, r = Tx.ln_fwd(e, None, net.ln.g.master, net.ln.b.master, net.c.eps, p_out=net.p_hidden,
                                seed=net.seed, salt_out=1)
         ctx.net = net
@@ -263,6 +275,17 @@ class _EmbedFn(torch.autograd.Function):
             net.ln_fin.run()
             for ln in net.all_lns():
                 ln.mark()
+        if net.packed:
+            # packed rows [T]: the position of a row is pos_ids[row], so the position table takes
+            # a gather's gradient like the other two (tail rows carry zero gradient)
+            dd = ds.float()
+            for tbl, ix in ((net.word, ids), (net.tok_type, tt), (net.pos, net.pos_ids)):
+                if _lib.DETERMINISTIC:
+                    tbl.grad.add_(_segment_sums(ix, dd, tbl.grad.shape[0]))
+                else:
+                    tbl.grad.index_add_(0, ix, dd)
+                net.ctx.arena.mark_ready(tbl)
+            return None, None, None, None
         B, S = ids.shape
         if not _lib.DETERMINISTIC and net.tok_type.grad.shape[0] <= 4:
             # one kernel: word atomics, per-position and per-type sums (Tx.embed_bwd)
@@ -301,6 +324,8 @@ class _HeadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, anchor, labels, net: 'NativeBert'):
+        if net.packed:
+            return _HeadFn.forward_packed(ctx, h, labels, net)
         B, S = net.B, net.S
         cls = h.view(B, S, -1)[:, 0].contiguous()
         z, _ = net.pooler.fwd(cls)
@@ -314,6 +339,36 @@ class _HeadFn(torch.autograd.Function):
         ctx.save_for_backward(cls, pooled, pd, dl)
         net._logits = logits
         return (net.loss_sum() / B).sum()
+
+    @staticmethod
+    def forward_packed(ctx, h, labels, net: 'NativeBert'):
+        """The packed head: [CLS] is row cu[b] of slot b, and the loss is the mean over the real
+        sequences - every slot's cross-entropy weighted by ``slot_w`` (1/nseq, 0 for an empty
+        slot).  The fused softmax-CE kernel scales every row by one 1/B and accumulates every
+        row, so the [nseq_max, labels] logits take torch ops on fp32 here, as the generic
+        engine's criterion does; the cost is a few tiny launches."""
+        V = net.c.num_labels
+        cls = h[net.cls_rows()]
+        z, _ = net.pooler.fwd(cls)
+        net.ctx.refresh_wt()
+        pooled = torch.tanh(z.float()).to(torch.bfloat16)
+        pd = Tx.dropout(pooled, net.p_hidden, net.seed, 2)
+        logits = Fn.linear_fwd(pd, net.cls_w.bf16, net.cls_b.master)
+        lf = logits[:, :V].float()
+        w = net.slot_w
+        real = (w > 0).float()
+        logp = torch.log_softmax(lf, 1)
+        nll = -logp.gather(1, labels[:, None])[:, 0]
+        net.loss_sum().add_((nll * real).sum())          # summed over the real sequences, like the padded head
+        net.correct().add_(((lf.argmax(1) == labels).float() * real).sum())
+        g = torch.exp(logp)
+        g.scatter_add_(1, labels[:, None], torch.full_like(nll, -1.0)[:, None])
+        dl = torch.zeros_like(logits, dtype=torch.bfloat16)
+        dl[:, :V] = (g * w[:, None]).to(torch.bfloat16)  # an empty slot: exactly zero
+        ctx.net = net
+        ctx.save_for_backward(cls, pooled, pd, dl)
+        net._logits = logits
+        return (nll * w).sum()
 
     @staticmethod
     def backward(ctx, g):
@@ -330,6 +385,12 @@ class _HeadFn(torch.autograd.Function):
         net.pooler.bwd_params(dz, cls)
         dcls = net.pooler.dgrad(dz)
         net.pooler.mark()
+        if net.packed:
+            # dcls of an empty slot is exactly zero (its dlogits are), so adding it to whichever
+            # row that slot gathered changes nothing; real slots own distinct rows
+            dh = torch.zeros(net.T, dcls.shape[1], device=dcls.device, dtype=torch.float32)
+            dh.index_add_(0, net.cls_rows(), dcls.float())
+            return dh.to(torch.bfloat16), None, None, None
         dh = torch.zeros(net.B, net.S, dcls.shape[1], device=dcls.device, dtype=torch.bfloat16)
         dh[:, 0] = dcls
         return dh.view(net.B * net.S, -1), None, None, None
@@ -349,11 +410,35 @@ def native_bert_unsupported(c, seq_len: int = 1):
 
 
 class NativeBert:
-    def __init__(self, model: BertForSequenceClassification, device, batch: int, seq_len: int):
+    """``packed_tokens=T`` selects packed mode: the activations are ``T`` rows of sequences laid
+    back to back (no padding rows between them), ``batch`` is then the most sequences one step
+    holds (``nseq_max``) and ``seq_len`` the longest one (``max_len``).  What varies per batch -
+    ``cu`` (int32 [nseq_max + 1]), ``pos_ids`` ([T], position within the sequence, 0 in the
+    unused tail) and ``slot_w`` ([nseq_max], 1/nseq for a real slot, 0 for an empty one) -
+    lives in device memory and is copied into outside the graph, so one captured graph serves
+    every mix of lengths.  ``T`` must be a multiple of 8 (the GEMMs read rows and the weight
+    gradients reduce over them in 16-byte chunks) and fit the position table."""
+
+    def __init__(self, model: BertForSequenceClassification, device, batch: int, seq_len: int,
+                 packed_tokens: Optional[int] = None):
         c = model.config
         unsupported = native_bert_unsupported(c, seq_len)
         if unsupported:
             raise NativeUnsupported(unsupported)
+        self.packed = packed_tokens is not None
+        if self.packed:
+            T = int(packed_tokens)
+            if T < 8 or T % 8:
+                raise NativeUnsupported(f'pack_tokens {T}: the native GEMMs need a row count that is a positive '
+                                        'multiple of 8')
+            if seq_len > model.pos.weight.shape[0]:
+                raise NativeUnsupported(f'max_len {seq_len} is past the {model.pos.weight.shape[0]} positions of '
+                                        'the model')
+            if batch < 1:
+                raise NativeUnsupported(f'packed mode needs room for at least one sequence (nseq_max {batch})')
+            self.T = T
+        else:
+            self.T = batch * seq_len
         self.model, self.c = model, c
         self.B, self.S = batch, seq_len
         self.p_hidden, self.p_attn = c.hidden_dropout, c.attention_dropout
@@ -382,6 +467,11 @@ class NativeBert:
         ctx.default_dgrad_first(True)
         self.device = ctx.device
         self.seed = torch.zeros(1, device=self.device, dtype=torch.int32)
+        self.cu = self.pos_ids = self.slot_w = None
+        if self.packed:   # one empty batch until the step loads a real one
+            self.cu = torch.zeros(batch + 1, device=self.device, dtype=torch.int32)
+            self.pos_ids = torch.zeros(self.T, device=self.device, dtype=torch.long)
+            self.slot_w = torch.zeros(batch, device=self.device, dtype=torch.float32)
         self.ln_fin = Tx.LnFinalizer()
         for ln in self.all_lns():
             self.ln_fin.add(ctx.ws[ln.k_sums], ln.g.grad, ln.b.grad)
@@ -444,6 +534,24 @@ class NativeBert:
     def eval(self):
         self.train(False)
 
+    # ------------------------------------------------------------------ embedding / [CLS] rows
+    def embed(self, ids, tt, pos_ids=None):
+        """Summed word + position + token-type embeddings as [rows, hidden] bf16: ``ids`` / ``tt``
+        [B, S] (position = column), or packed [T] with the position of every row in ``pos_ids``
+        (default: this engine's static ``pos_ids``)."""
+        if ids.dim() == 1:
+            pos = self.pos.bf16[self.pos_ids if pos_ids is None else pos_ids]
+        else:
+            pos = self.pos.bf16[:ids.shape[1]][None]
+        e = self.word.bf16[ids].float() + pos.float() + self.tok_type.bf16[tt].float()
+        return e.to(torch.bfloat16).view(ids.numel(), -1)
+
+    def cls_rows(self, cu=None):
+        """Packed mode: the row of every slot's first token, cu[b]; an empty slot (whose cu[b]
+        may equal T) gathers the last row instead - any valid row does, its weight is 0."""
+        cu = self.cu if cu is None else cu
+        return cu[:-1].long().clamp(max=self.T - 1)
+
     # ------------------------------------------------------------------ graph
     def loss(self, ids, tt, key_bias, labels):
         h = _EmbedFn.apply(ids, tt, self.ctx.anchor, self)
@@ -478,6 +586,27 @@ class NativeBert:
         finally:
             self.B, self.S = saved[0], saved[1]
             self.train(saved[2])
+
+    def predict_packed(self, ids, tt, pos_ids, cu, max_len: int):
+        """:meth:`predict` over packed rows: ``ids`` / ``tt`` / ``pos_ids`` [T'] (T' a multiple
+        of 8, any size: nothing here is captured) and ``cu`` int32 [n + 1] on the device; fp32
+        logits [n, num_labels], one row per slot."""
+        saved = (self.B, self.S, self.T, self.cu, self.ctx.training)
+        self.B, self.S, self.T, self.cu = cu.numel() - 1, int(max_len), ids.numel(), cu
+        self.train(False)
+        try:
+            with torch.no_grad():
+                h = Tx.ln_fwd(self.embed(ids, tt, pos_ids), None, self.ln.g.master, self.ln.b.master, self.c.eps,
+                              p_out=0.0, seed=self.seed, salt_out=1)[0]
+                for layer in self.layers:
+                    h, _ = layer.fwd(h, None)
+                z, _ = self.pooler.fwd(h[self.cls_rows()])
+                pooled = torch.tanh(z.float()).to(torch.bfloat16)
+                logits = Fn.linear_fwd(pooled, self.cls_w.bf16, self.cls_b.master)
+            return logits[:, :self.c.num_labels].float()
+        finally:
+            self.B, self.S, self.T, self.cu = saved[:4]
+            self.train(saved[4])
 
 
 __all__ = ['NativeBert']

@@ -75,6 +75,8 @@ _SIGS = {
     'mlc_flash_bwd': [vp] * 7 + [i32] * 4 + [f32, f32, vp, u32, vp],
     'mlc_flash_fwd_masked': [vp] * 4 + [i32] * 4 + [f32, f32, vp, u32, i32, vp, i64, i64, vp],
     'mlc_flash_bwd_masked': [vp] * 7 + [i32] * 4 + [f32, f32, vp, u32, i32, vp, i64, i64, vp],
+    'mlc_flash_fwd_varlen': [vp] * 4 + [i32] * 5 + [f32, f32, vp, u32, i32, vp],
+    'mlc_flash_bwd_varlen': [vp] * 7 + [i32] * 5 + [f32, f32, vp, u32, i32, vp],
     'mlc_flash_bwd128': [i32],
     'mlc_colsum_acc': [vp, vp, vp, i32, i32, vp],
     'mlc_dropout': [vp, vp, i64, f32, vp, u32, vp],

@@ -390,6 +390,134 @@ def attn_bwd(qkv, key_bias, dctx, lse, B, S, H, scale, p=0.0, seed=None, salt=0,
     return dqkv.to(torch.bfloat16)
 
 
+# ---------------------------------------------------------------------------- packed (varlen) attention
+def check_cu_seqlens(cu_seqlens, T: int, max_len: int):
+    """``cu_seqlens`` (int32 [nseq_max + 1]: sequence b owns rows cu[b] .. cu[b+1]-1 of a
+    [T]-row buffer) checked while it is still on the host: starts at 0, non-decreasing, ends
+    within ``T``, every length <= ``max_len``.  ValueError otherwise.  The kernels clamp what
+    they read from device memory, so a bad vector there costs wrong numbers, never a fault; a
+    vector that is already on the device is not read back."""
+    if cu_seqlens.dim() != 1 or cu_seqlens.numel() < 2 or cu_seqlens.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f'cu_seqlens: a 1-D int32 vector of nseq_max + 1 entries, not {tuple(cu_seqlens.shape)} '
+                         f'{cu_seqlens.dtype}')
+    if cu_seqlens.device.type != 'cpu':
+        return
+    cu = cu_seqlens.tolist()
+    lens = [b - a for a, b in zip(cu, cu[1:])]
+    if cu[0] != 0 or min(lens) < 0:
+        raise ValueError(f'cu_seqlens must start at 0 and be non-decreasing (got {cu})')
+    if cu[-1] > T:
+        raise ValueError(f'cu_seqlens ends at row {cu[-1]}, past the {T} rows of the buffer')
+    if max(lens) > max_len:
+        raise ValueError(f'a sequence of {max(lens)} rows is over max_len {max_len}')
+
+
+def _no_bias_with_cu(key_bias, attn_bias):
+    if key_bias is not None or attn_bias is not None:
+        raise ValueError('the packed (cu_seqlens) attention takes no key_bias / attn_bias: sequences are '
+                         'delimited by cu_seqlens, and additive masks are not part of the varlen kernels')
+
+
+def _seq_keep(b, H, L, max_len, p, seed, salt):
+    """Keep mask [H, L, L] of packed sequence b: the padded layout's element index at
+    S = max_len, ((b*H + h)*max_len + q)*max_len + key."""
+    h = torch.arange(H, dtype=torch.int64)[:, None, None]
+    q = torch.arange(L, dtype=torch.int64)[None, :, None]
+    k = torch.arange(L, dtype=torch.int64)[None, None, :]
+    idx = ((b * H + h) * max_len + q) * max_len + k
+    return (_hash(_seed_val(seed), salt, idx) >> 8) >= int(p * 16777216.0)
+
+
+def _seq_slices(cu_seqlens):
+    cu = cu_seqlens.tolist()
+    return [(b, c0, c1) for b, (c0, c1) in enumerate(zip(cu, cu[1:])) if c1 > c0]
+
+
+def attn_fwd_varlen(qkv, cu_seqlens, max_len, H, scale, p=0.0, seed=None, salt=0, head_dim: int = 64, *,
+                    causal: bool = False, key_bias=None, attn_bias=None):
+    """Fused attention over packed sequences: ``qkv`` [T, 3*H*D] holds the sequences back to
+    back, sequence b in rows cu_seqlens[b] .. cu_seqlens[b+1]-1 (int32 [nseq_max + 1]; equal
+    neighbours = an empty slot), every length <= ``max_len``.  Returns (ctx [T, H*D] bf16, lse
+    [H*T] fp32, index h*T + row).  Rows that belong to no sequence (cu[-1] .. T-1) come back as
+    exact zeros (zero-filled outputs; the kernels write real rows only).  Dropout drops element
+    ((b*H + h)*max_len + q)*max_len + key with q / key relative to the sequence - exactly what
+    :func:`attn_fwd` over the same sequences padded to S = max_len drops.  ``causal`` as in
+    :func:`attn_fwd`; bias operands are refused (ValueError).  ``cu_seqlens`` is validated
+    (:func:`check_cu_seqlens`) when it arrives on the host."""
+    _no_bias_with_cu(key_bias, attn_bias)
+    D, T = head_dim, qkv.shape[0]
+    check_cu_seqlens(cu_seqlens, T, max_len)
+    nseq = cu_seqlens.numel() - 1
+    if _cuda(qkv) and D not in (64, 128):
+        assert attn_supported(max_len, D), (max_len, D)
+        Dp = _pad_dim(D)
+        ctx, lse = attn_fwd_varlen(_pad_heads(qkv, T, 3, H, D, Dp), cu_seqlens, max_len, H, scale, p, seed, salt, Dp,
+                                   causal=causal)
+        return _unpad_heads(ctx, T, 1, H, D, Dp), lse
+    if _cuda(qkv):
+        assert attn_supported(max_len, D) and qkv.is_contiguous() and tuple(qkv.shape) == (T, 3 * H * D)
+        cu = cu_seqlens.to(device=qkv.device, dtype=torch.int32).contiguous()
+        ctx = torch.zeros(T, H * D, device=qkv.device, dtype=torch.bfloat16)
+        lse = torch.zeros(H * T, device=qkv.device, dtype=torch.float32)
+        _lib.call('mlc_flash_fwd_varlen', _lib.ptr(qkv), _lib.ptr(cu), _lib.ptr(ctx), _lib.ptr(lse), T, nseq,
+                  int(max_len), H, D, float(scale), float(p), _lib.ptr(seed), salt, int(bool(causal)), _lib.stream())
+        return ctx, lse
+    ctx = torch.zeros(T, H * D)
+    lse = torch.zeros(H, T)
+    for b, c0, c1 in _seq_slices(cu_seqlens):
+        L = c1 - c0
+        q, k, v, x = _attn_ref_scores(qkv[c0:c1], None, 1, L, H, scale, D, causal)
+        P = torch.softmax(x, -1)
+        if p > 0:
+            P = torch.where(_seq_keep(b, H, L, max_len, p, seed, salt)[None], P / (1 - p), torch.zeros_like(P))
+        ctx[c0:c1] = torch.matmul(P, v).permute(0, 2, 1, 3).reshape(L, H * D)
+        lse[:, c0:c1] = torch.logsumexp(x, -1)[0]
+    return ctx.to(torch.bfloat16), lse.reshape(-1)
+
+
+def attn_bwd_varlen(qkv, cu_seqlens, max_len, dctx, lse, H, scale, p=0.0, seed=None, salt=0, head_dim: int = 64,
+                    ctx=None, *, causal: bool = False, key_bias=None, attn_bias=None):
+    """Gradient of :func:`attn_fwd_varlen` wrt ``qkv``: dqkv [T, 3*H*D] bf16, exact zeros in
+    the rows of no sequence.  ``ctx`` is the forward's output (the kernels need it)."""
+    _no_bias_with_cu(key_bias, attn_bias)
+    D, T = head_dim, qkv.shape[0]
+    check_cu_seqlens(cu_seqlens, T, max_len)
+    nseq = cu_seqlens.numel() - 1
+    if _cuda(qkv) and D not in (64, 128):
+        assert attn_supported(max_len, D) and ctx is not None, (max_len, D)
+        Dp = _pad_dim(D)
+        dq = attn_bwd_varlen(_pad_heads(qkv, T, 3, H, D, Dp), cu_seqlens, max_len, _pad_heads(dctx, T, 1, H, D, Dp),
+                             lse, H, scale, p, seed, salt, Dp, ctx=_pad_heads(ctx, T, 1, H, D, Dp), causal=causal)
+        return _unpad_heads(dq, T, 3, H, D, Dp)
+    if _cuda(qkv):
+        assert attn_supported(max_len, D) and qkv.is_contiguous() and tuple(qkv.shape) == (T, 3 * H * D)
+        assert dctx.is_contiguous() and tuple(dctx.shape) == (T, H * D) and lse.numel() == H * T
+        assert ctx is not None and ctx.is_contiguous() and ctx.shape == dctx.shape
+        cu = cu_seqlens.to(device=qkv.device, dtype=torch.int32).contiguous()
+        dqkv = torch.zeros_like(qkv)
+        dot = torch.empty(H * T, device=qkv.device, dtype=torch.float32)
+        _lib.call('mlc_flash_bwd_varlen', _lib.ptr(qkv), _lib.ptr(cu), _lib.ptr(ctx), _lib.ptr(dctx), _lib.ptr(lse),
+                  _lib.ptr(dot), _lib.ptr(dqkv), T, nseq, int(max_len), H, D, float(scale), float(p), _lib.ptr(seed),
+                  salt, int(bool(causal)), _lib.stream())
+        return dqkv
+    E = H * D
+    dqkv = torch.zeros(T, 3 * E)
+    for b, c0, c1 in _seq_slices(cu_seqlens):
+        L = c1 - c0
+        q, k, v, P, _ = _attn_ref_probs(qkv[c0:c1], None, 1, L, H, scale, D, causal)
+        do = dctx[c0:c1].float().view(1, L, H, D).permute(0, 2, 1, 3)
+        m = _seq_keep(b, H, L, max_len, p, seed, salt)[None] if p > 0 else None
+        Pd = torch.where(m, P / (1 - p), torch.zeros_like(P)) if m is not None else P
+        dv = torch.matmul(Pd.transpose(-1, -2), do)
+        dPd = torch.matmul(do, v.transpose(-1, -2))
+        dP = torch.where(m, dPd / (1 - p), torch.zeros_like(dPd)) if m is not None else dPd
+        dS = scale * P * (dP - (P * dP).sum(-1, keepdim=True))
+        dq = torch.matmul(dS, k)
+        dk = torch.matmul(dS.transpose(-1, -2), q)
+        dqkv[c0:c1] = torch.stack([dq, dk, dv]).permute(1, 3, 0, 2, 4).reshape(L, 3 * E)
+    return dqkv.to(torch.bfloat16)
+
+
 # ---------------------------------------------------------------------------- dense layers
 _WS = {}
 _WS_OLD = []   # superseded buffers stay alive: a captured graph may still point at them
@@ -526,4 +654,4 @@ def dropout(x, p, seed, salt):
 
 
 __all__ = ['ln_fwd', 'ln_bwd', 'LnFinalizer', 'embed_bwd', 'softmax_fwd', 'softmax_bwd', 'dense_fwd', 'dense_dgrad', 'dact_gelu', 'colsum_acc',
-           'dropout', 'keep_mask']
+           'dropout', 'keep_mask', 'attn_fwd_varlen', 'attn_bwd_varlen', 'check_cu_seqlens']

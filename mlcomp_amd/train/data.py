@@ -45,10 +45,14 @@ class SyntheticClassification(Dataset):
 @register_dataset('synthetic_text_classification')
 class SyntheticTextClassification(Dataset):
     """Random token ids (two segments) with labels; ``learnable`` makes the label a
-    function of the first token so fine-tuning has signal."""
+    function of the first token so fine-tuning has signal.  Every row is full length unless
+    ``pad_fraction`` (lengths uniform in [seq_len * (1 - pad_fraction), seq_len]) or ``lengths``
+    is given: ``{'min': a, 'max': b}`` draws them uniformly in [a, b] (seeded; defaults 2 and
+    seq_len), a list gives them outright (cycled over the samples).  Shorter rows are
+    right-padded: id 0, token type 0, attention_mask 0."""
 
     def __init__(self, num_samples=256, seq_len=128, vocab_size=30522, num_classes=2, seed=0, learnable=True,
-                 pad_fraction=0.0, **_):
+                 pad_fraction=0.0, lengths=None, **_):
         g = torch.Generator().manual_seed(seed)
         self.ids = torch.randint(1, vocab_size, (num_samples, seq_len), generator=g)
         self.y = (self.ids[:, 1] % num_classes) if learnable else torch.randint(0, num_classes, (num_samples,),
@@ -59,6 +63,21 @@ class SyntheticTextClassification(Dataset):
         if pad_fraction > 0:
             lens = torch.randint(int(seq_len * (1 - pad_fraction)), seq_len + 1, (num_samples,), generator=g)
             self.mask = (torch.arange(seq_len)[None] < lens[:, None]).long()
+        if lengths is not None:
+            if isinstance(lengths, dict):
+                lo, hi = int(lengths.get('min', 2)), int(lengths.get('max', seq_len))
+                lens = torch.randint(lo, hi + 1, (num_samples,), generator=g)
+            else:
+                lens = torch.tensor([int(lengths[i % len(lengths)]) for i in range(num_samples)])
+            if int(lens.min()) < 1 or int(lens.max()) > seq_len:
+                raise ValueError(f'lengths must lie in [1, seq_len = {seq_len}]')
+            self.mask = (torch.arange(seq_len)[None] < lens[:, None]).long()
+            self.ids = self.ids * self.mask
+            self.tt = self.tt * self.mask
+
+    def lengths(self):
+        """Token count of every sample (what a length-aware batch sampler fills its budget with)."""
+        return self.mask.sum(1).tolist()
 
     def __len__(self):
         return len(self.y)
@@ -144,6 +163,69 @@ class DistributedSamplerIndices(Sampler):
         self.epoch = epoch
 
 
+class TokenBudgetBatchSampler(Sampler):
+    """Batches of whole sequences for the packed BERT engine: walks the dataset in order (or
+    in an epoch-seeded shuffle) and greedily fills each step with sequences until the next one
+    would pass ``max_tokens`` or the step holds ``max_seqs`` - no bin-packing search, so a
+    step is on average half a sequence short of its budget.  Every index is yielded exactly
+    once per epoch.  ``lengths[i]`` is the token count of sample i (none may exceed
+    ``max_tokens``).  With ``world_size > 1`` rank r takes every world_size-th index of the
+    epoch's order and all ranks run the step count of the rank with the fewest steps (the
+    collectives need equal counts; the few sequences past it wait for the next epoch's
+    shuffle)."""
+
+    def __init__(self, lengths, max_tokens: int, max_seqs: int, shuffle: bool = False, seed: int = 0,
+                 rank: int = 0, world_size: int = 1):
+        self.lengths = [int(v) for v in lengths]
+        self.max_tokens, self.max_seqs = int(max_tokens), int(max_seqs)
+        if self.max_seqs < 1:
+            raise ValueError('max_seqs must be at least 1')
+        if self.lengths and max(self.lengths) > self.max_tokens:
+            raise ValueError(f'a sequence of {max(self.lengths)} tokens does not fit a step of {self.max_tokens}')
+        self.shuffle, self.seed, self.rank, self.world = shuffle, seed, rank, world_size
+        self.epoch = 0
+
+    def set_epoch(self, epoch: int):
+        self.epoch = epoch
+
+    def _fill(self, order):
+        out, cur, tokens = [], [], 0
+        for i in order:
+            n = self.lengths[i]
+            if cur and (tokens + n > self.max_tokens or len(cur) == self.max_seqs):
+                out.append(cur)
+                cur, tokens = [], 0
+            cur.append(i)
+            tokens += n
+        if cur:
+            out.append(cur)
+        return out
+
+    def _batches(self):
+        order = list(range(len(self.lengths)))
+        if self.shuffle:
+            g = torch.Generator().manual_seed(self.seed + self.epoch)
+            order = torch.randperm(len(order), generator=g).tolist()
+        if self.world <= 1:
+            return self._fill(order)
+        per_rank = [self._fill(order[r::self.world]) for r in range(self.world)]
+        return per_rank[self.rank][:min(len(b) for b in per_rank)]
+
+    def __iter__(self):
+        return iter(self._batches())
+
+    def __len__(self):
+        return len(self._batches())
+
+
+def sequence_lengths(dataset):
+    """Token counts of a text dataset's samples: its own ``lengths()`` when it has one, else
+    the sum of every sample's ``attention_mask``."""
+    if hasattr(dataset, 'lengths'):
+        return [int(v) for v in dataset.lengths()]
+    return [int(torch.as_tensor(dataset[i]['attention_mask']).sum()) for i in range(len(dataset))]
+
+
 def collate_dict(batch):
     if isinstance(batch[0], (tuple, list)):   # torchvision-style (x, y) samples
         batch = [{'features': b[0], 'targets': b[1]} for b in batch]
@@ -177,4 +259,5 @@ def make_loader(dataset, batch_size, shuffle, num_workers=0, world_size=1, rank=
 
 __all__ = ['DATASETS', 'register_dataset', 'SyntheticClassification', 'SyntheticTextClassification',
            'SyntheticSegmentation', 'DeviceSyntheticLoader',
-           'DistributedSamplerIndices', 'make_loader', 'collate_dict']
+           'DistributedSamplerIndices', 'TokenBudgetBatchSampler', 'sequence_lengths', 'make_loader',
+           'collate_dict']

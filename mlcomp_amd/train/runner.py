@@ -23,6 +23,7 @@ Two engines behind one loop:
 from __future__ import annotations
 
 import logging
+import os
 import time
 from collections import OrderedDict, defaultdict
 from typing import Dict, List, Optional
@@ -99,10 +100,17 @@ class State:
         return self.runner.current_lr()
 
 
+def _native_device(device: torch.device) -> bool:
+    """The native engines run on a GPU; MLC_NATIVE_CPU=1 also lets a stage select their fp32
+    CPU twins (the same step code over the ops' reference paths: for tests and debugging, far
+    too slow to train with)."""
+    return device.type == 'cuda' or os.environ.get('MLC_NATIVE_CPU', '0') == '1'
+
+
 def _native_kind(model: nn.Module, device: torch.device) -> Optional[str]:
     """'resnet' / 'bert' / 'unet' (U-Net, LinkNet, FPN, PSPNet, DeepLab segmentation) when the model runs on a
     native engine on this device."""
-    if device.type != 'cuda':
+    if not _native_device(device):
         return None
     from mlcomp_amd.models.bert import BertForSequenceClassification
     from mlcomp_amd.models.resnet import ResNet
@@ -208,7 +216,7 @@ class Runner:
         elif self.precision != 'bf16':
             reason = f'precision {self.precision}: the native engines compute in bf16 (fp32 master weights)'
         elif kind is None:
-            reason = ('no HIP device: the native engines run on MI355X GPUs' if self.device.type != 'cuda' else
+            reason = ('no HIP device: the native engines run on MI355X GPUs' if not _native_device(self.device) else
                       f'{type(self.model).__name__} has no native lowering: {_generic_reason(self.model)}')
         if reason is None:
             from .native_spec import NativeUnsupported, native_plan
@@ -216,14 +224,28 @@ class Runner:
                 self._native_plan = native_plan(self.experiment, stage, kind)
             except NativeUnsupported as e:
                 reason = str(e)
-        if reason is None and self.device.type != 'cuda':
+        if reason is None and not _native_device(self.device):
             reason = 'no HIP device: the native engines run on MI355X GPUs'
+        pack = self.experiment.args.get('pack_tokens')
+        if pack is not None and reason is None and kind != 'bert':
+            # packed variable-length batches exist on the BERT engine only
+            if forced:
+                raise RuntimeError(f'engine: native cannot run stage {stage!r}: args.pack_tokens needs the native '
+                                   f'BERT engine, and this model runs on the {kind} engine')
+            _log.warning('stage %s: args.pack_tokens ignored - the %s engine has no packed mode', stage, kind)
+            pack = None
         if reason is not None and forced:
             raise RuntimeError(f'engine: native cannot run stage {stage!r}: {reason}')
         if reason is not None:
+            if pack is not None:
+                _log.warning('stage %s: args.pack_tokens ignored - the PyTorch engine has no packed mode', stage)
             return {'stage': stage, 'engine': 'torch', 'kind': None, 'precision': self.precision,
                     'reason': reason}
-        return {'stage': stage, 'engine': 'native', 'kind': kind, 'precision': 'bf16', 'reason': None}
+        choice = {'stage': stage, 'engine': 'native', 'kind': kind, 'precision': 'bf16', 'reason': None}
+        if pack is not None:
+            choice['pack_tokens'] = int(pack)
+            _log.info('stage %s: native BERT engine in packed mode, %d tokens per step', stage, int(pack))
+        return choice
 
     def _build_model(self, stage):
         if self.model is None:
@@ -232,6 +254,7 @@ class Runner:
         choice = self._select_engine(stage)
         use_native = choice['engine'] == 'native'
         self.native_kind = choice['kind']
+        self.pack_tokens = choice.get('pack_tokens')
         self.engine_log.append(choice)
         if choice['reason'] and self.engine == 'auto' and self.device.type == 'cuda':
             _log.warning('stage %s: %s - training on the PyTorch engine', stage, choice['reason'])
@@ -263,8 +286,14 @@ class Runner:
             from .native_bert_step import NativeBertStep
             ids = batch['input_ids']
             self.model.to(self.device)
+            nseq = ids.shape[0]
+            if self.pack_tokens is not None:
+                # packed mode: data_params.batch_size is the most sequences a step holds (the
+                # first batch may hold fewer), the row count is the token budget
+                plan['pack_tokens'] = self.pack_tokens
+                nseq = int(self.experiment.stage_params(self.state.stage, 'data_params').get('batch_size', 32))
             self.native_step = NativeBertStep(
-                torch_model=self.model, batch=ids.shape[0], seq_len=ids.shape[1], device=self.device,
+                torch_model=self.model, batch=max(nseq, ids.shape[0]), seq_len=ids.shape[1], device=self.device,
                 world_size=self.world_size, num_labels=self.model.config.num_labels, use_graph=use_graph, **plan)
             self._apply_native_opt_state()
             return
@@ -336,6 +365,16 @@ class Runner:
                 ds, sampler = ds['dataset'], ds.get('sampler')
             else:
                 sampler = None
+            if getattr(self, 'pack_tokens', None) is not None and name.startswith('train') and sampler is None:
+                # packed BERT engine: whole sequences up to the token budget, at most batch_size of them
+                from torch.utils.data import DataLoader
+                from .data import TokenBudgetBatchSampler, collate_dict, sequence_lengths
+                bsamp = TokenBudgetBatchSampler(sequence_lengths(ds), self.pack_tokens, bs, shuffle=True,
+                                                seed=int(dp.get('seed', 0)), rank=self.rank,
+                                                world_size=self.world_size)
+                out[name] = DataLoader(ds, batch_sampler=bsamp, num_workers=int(dp.get('num_workers', 0)),
+                                       collate_fn=collate_dict)
+                continue
             out[name] = make_loader(ds, bs, shuffle=name.startswith('train'), sampler=sampler,
                                     num_workers=int(dp.get('num_workers', 0)), world_size=self.world_size,
                                     rank=self.rank, drop_last=self.state.native and name.startswith('train'))
@@ -509,6 +548,8 @@ class Runner:
         st.loader_len = len(loader)
         if hasattr(getattr(loader, 'sampler', None), 'set_epoch'):
             loader.sampler.set_epoch(st.epoch)
+        if hasattr(getattr(loader, 'batch_sampler', None), 'set_epoch'):
+            loader.batch_sampler.set_epoch(st.epoch)
         st.loader_metrics = {}
         sums, count = defaultdict(float), 0
         dev_loss = dev_correct = None
@@ -566,12 +607,13 @@ class Runner:
                     ns.load_batch(batch['features'], batch['targets'])
                     head = ns.net.head
                 ns()
-                st.batch_size = ns.batch
+                # a packed BERT step trains on however many sequences its token budget took
+                st.batch_size = ns.samples() if self.native_kind == 'bert' else ns.batch
                 if dev_loss is None:
                     dev_loss = torch.zeros(2, device=self.device)
                 dev_loss[0] += head.loss_sum()[0]
                 dev_loss[1] += head.correct()[0]
-                n_samples += ns.batch
+                n_samples += st.batch_size
             elif st.native:
                 self._run_native_eval(batch)
             else:
