@@ -36,6 +36,21 @@
 // params[batch][8] = {y0, x0, h, w, flip, t0, s, 0}.  The gather threads copy only the T
 // frames t0 + k*s, so a slot's image buffer is [batch][T][H][W][C].
 //
+// Text files: magic "MLTXT001", H = the longest record in tokens, W = vocab_size, C =
+// token_bytes (2: u16, only for vocab <= 65536; 4: u32), label_bytes = 4, record_bytes = 0
+// (records vary in length), reserved[0..7] = u64 total_tokens.  After the header come
+// `count` index entries {u64 token_offset; u32 length; u32 type0_length; i32 label; u32 zero}
+// (tokens [0, type0_length) of a record have token type 0, the rest type 1), then
+// total_tokens tokens.  mlr_text_open checks every entry.  The text loader (mlr_text_*) runs
+// the same slot state machine, but a batch is a token budget: start_epoch plans the epoch
+// (seeded order, rank r takes every world-th entry without padding, batches filled greedily
+// until the next sequence would pass max_tokens or the batch holds max_seqs; in training all
+// ranks run the step count of the rank with the fewest) and the gather threads write
+// sequences at the offsets of the plan.  A slot is one int32 buffer, so a batch crosses PCIe
+// in one copy: {nseq, total}, {length, type0_length, label}[max_seqs], tokens[max_tokens]
+// widened to int32, then (8-byte aligned, host only) int64 indices[max_seqs].  Rows past
+// `total` and entries past `nseq` keep whatever an earlier batch left there.
+//
 // Slot protocol: the caller registers `depth` slots (image buffer of batch*H*W*C bytes,
 // int64 labels[batch], int32 params[batch][5]); next() blocks until the next batch of the
 // epoch (in order) is complete and returns its slot, release(slot) hands it back.  Batches
@@ -62,8 +77,9 @@ namespace {
 constexpr char MAGIC[8] = {'M', 'L', 'R', 'E', 'C', '0', '0', '1'};
 constexpr char SEG_MAGIC[8] = {'M', 'L', 'S', 'E', 'G', '0', '0', '1'};
 constexpr char CLIP_MAGIC[8] = {'M', 'L', 'V', 'I', 'D', '0', '0', '1'};
+constexpr char TEXT_MAGIC[8] = {'M', 'L', 'T', 'X', 'T', '0', '0', '1'};
 
-enum Kind { LABELS = 0, SEG = 1, CLIP = 2 };   // what a record holds next to its image(s)
+enum Kind { LABELS = 0, SEG = 1, CLIP = 2, TEXT = 3 };   // what a record holds next to its image(s)
 
 struct Header {
   char magic[8];
@@ -73,6 +89,14 @@ struct Header {
 };
 static_assert(sizeof(Header) == 64, "header layout");
 
+struct TextEntry {   // one index entry of a text file
+  uint64_t token_offset;
+  uint32_t length, type0_length;
+  int32_t label;
+  uint32_t zero;
+};
+static_assert(sizeof(TextEntry) == 24, "index entry layout");
+
 struct RecordFile {
   int fd = -1;
   const uint8_t* map = nullptr;
@@ -80,7 +104,10 @@ struct RecordFile {
   Header h{};
   uint32_t K = 0, kind = 0;   // mask planes and kind of a segmentation file (K = 0: labels)
   uint32_t F = 0;             // frames per record of a clip file (0: not a clip file)
-  Kind what() const { return F ? CLIP : K ? SEG : LABELS; }
+  const TextEntry* index = nullptr;   // text file: `count` entries, then the tokens
+  const uint8_t* tokens = nullptr;
+  uint64_t total_tokens = 0;
+  Kind what() const { return index ? TEXT : F ? CLIP : K ? SEG : LABELS; }
   const uint8_t* record(uint64_t i) const { return map + sizeof(Header) + i * h.record_bytes; }
 };
 
@@ -106,6 +133,7 @@ struct Slot {
   int64_t* lab = nullptr;    // classification
   uint8_t* mask = nullptr;   // segmentation
   int32_t* par = nullptr;
+  int32_t* txt = nullptr;    // text: the whole slot
   SlotState state = FREE;
   int64_t batch = -1;
   int remaining = 0;   // chunks still being filled
@@ -121,6 +149,10 @@ struct Loader {
   bool seg = false;   // image + mask records, params[batch][8]
   bool clip = false;  // clip records: clip_len frames at frame_stride, params[batch][8]
   int clip_len = 0, frame_stride = 1;
+  bool text = false;  // token-budget batches: `batch` is max_seqs, a batch's rows come from the plan
+  int max_tokens = 0;
+  std::vector<uint64_t> bstart;   // text: batch b holds order[bstart[b] .. bstart[b+1])
+  std::vector<int32_t> doff;      // text: token offset of order[k] inside its batch
   std::vector<Slot> slots;
   // epoch
   uint64_t epoch = 0;
@@ -176,7 +208,83 @@ struct Loader {
     p[0] = (H - s) / 2; p[1] = (W - s) / 2; p[2] = s; p[3] = s;
   }
 
+  size_t text_index_off() const { return ((size_t)2 + 3 * (size_t)batch + (size_t)max_tokens + 1) & ~(size_t)1; }
+
+  // greedy token-budget batches over `ord`, the rule of TokenBudgetBatchSampler._fill:
+  // starts[k] is the position of batch k's first sequence, the last entry ord.size()
+  void plan_batches(const std::vector<uint64_t>& ord, std::vector<uint64_t>& starts) const {
+    starts.assign(1, 0);
+    int n = 0;
+    int64_t tokens = 0;
+    for (size_t k = 0; k < ord.size(); ++k) {
+      const int64_t len = rf->index[ord[k]].length;
+      if (n && (tokens + len > max_tokens || n == batch)) {
+        starts.push_back(k);
+        n = 0;
+        tokens = 0;
+      }
+      ++n;
+      tokens += len;
+    }
+    if (n) starts.push_back(ord.size());
+  }
+
+  // this rank's share of the epoch order `all` and its batches (see the file comment)
+  void plan_text(const std::vector<uint64_t>& all) {
+    std::vector<uint64_t> mine, other, starts;
+    size_t steps = SIZE_MAX;
+    for (int r = 0; r < world; ++r) {
+      if (r != rank && !train) continue;   // evaluation: all of this rank's own batches
+      std::vector<uint64_t>& ord = r == rank ? mine : other;
+      ord.clear();
+      for (size_t i = (size_t)r; i < all.size(); i += (size_t)world) ord.push_back(all[i]);
+      plan_batches(ord, starts);
+      steps = std::min(steps, starts.size() - 1);
+      if (r == rank) bstart = starts;
+    }
+    bstart.resize(steps + 1);
+    mine.resize((size_t)bstart[steps]);
+    order = mine;
+    doff.assign(order.size(), 0);
+    for (size_t b = 0; b < steps; ++b) {
+      int32_t off = 0;
+      for (uint64_t k = bstart[b]; k < bstart[b + 1]; ++k) {
+        doff[(size_t)k] = off;
+        off += (int32_t)rf->index[order[(size_t)k]].length;
+      }
+    }
+    nbatches = (int64_t)steps;
+  }
+
+  void fill_text(Slot& sl, int64_t b, int c) {
+    const uint64_t p0 = bstart[(size_t)b], p1 = bstart[(size_t)b + 1];
+    const int n = (int)(p1 - p0);
+    int32_t* ent = sl.txt + 2;
+    int32_t* tok = ent + 3 * (size_t)batch;
+    int32_t* idx = sl.txt + text_index_off();
+    if (c == 0) {
+      sl.txt[0] = n;
+      sl.txt[1] = doff[(size_t)p1 - 1] + (int32_t)rf->index[order[(size_t)p1 - 1]].length;
+    }
+    const int i0 = c * chunk, i1 = std::min(n, i0 + chunk);
+    for (int i = i0; i < i1; ++i) {
+      const uint64_t s = order[(size_t)p0 + i];
+      const TextEntry& e = rf->index[s];
+      ent[3 * i] = (int32_t)e.length; ent[3 * i + 1] = (int32_t)e.type0_length; ent[3 * i + 2] = e.label;
+      int32_t* dst = tok + doff[(size_t)p0 + i];
+      if (rf->h.C == 2) {
+        const uint16_t* src = (const uint16_t*)rf->tokens + e.token_offset;
+        for (uint32_t t = 0; t < e.length; ++t) dst[t] = (int32_t)src[t];
+      } else {
+        std::memcpy(dst, (const uint32_t*)rf->tokens + e.token_offset, (size_t)e.length * 4);
+      }
+      const int64_t rec = (int64_t)s;
+      std::memcpy(idx + 2 * (size_t)i, &rec, 8);
+    }
+  }
+
   void fill(Slot& sl, int64_t b, int c) {
+    if (text) return fill_text(sl, b, c);
     const size_t ib = (size_t)rf->h.H * rf->h.W * rf->h.C;
     const size_t mb = (size_t)rf->h.H * rf->h.W * rf->K;
     const int i0 = c * chunk, i1 = std::min(batch, i0 + chunk);
@@ -247,6 +355,15 @@ struct Loader {
       Rng g(seed ^ 0x5851f42d4c957f2dull ^ (e * 0x2545f4914f6cdd1dull));
       for (uint64_t i = n; i > 1; --i) std::swap(all[i - 1], all[g.next() % i]);
     }
+    if (text) {
+      plan_text(all);
+      nitems = nbatches * chunks_per_batch();
+      next_item = 0;
+      consume_next = 0;
+      started = true;
+      cv_work.notify_all();
+      return;
+    }
     // shard: pad to a multiple of world (wrapping), rank takes every world-th sample
     const uint64_t per = (n + world - 1) / world;
     order.clear();
@@ -301,6 +418,29 @@ struct Loader {
 
 namespace {
 
+// the checks of a text file: header, sizes and every index entry
+bool open_text(RecordFile* rf) {
+  const Header& h = rf->h;
+  if (std::memcmp(h.magic, TEXT_MAGIC, 8) != 0 || h.count == 0 || h.label_bytes != 4 || h.record_bytes != 0) return false;
+  if (h.H == 0 || h.W == 0 || !(h.C == 4 || (h.C == 2 && h.W <= 65536))) return false;
+  uint64_t total;
+  std::memcpy(&total, h.reserved, 8);
+  const uint64_t body = rf->size - sizeof(Header);
+  if (h.count > body / sizeof(TextEntry)) return false;
+  if (total > (body - h.count * sizeof(TextEntry)) / h.C) return false;
+  const auto* index = (const TextEntry*)(rf->map + sizeof(Header));
+  for (uint64_t i = 0; i < h.count; ++i) {
+    const TextEntry& e = index[i];
+    if (e.length < 1 || e.length > h.H || e.type0_length > e.length || e.token_offset > total ||
+        e.length > total - e.token_offset)
+      return false;
+  }
+  rf->index = index;
+  rf->tokens = rf->map + sizeof(Header) + h.count * sizeof(TextEntry);
+  rf->total_tokens = total;
+  return true;
+}
+
 RecordFile* open_file(const char* path, Kind kind) {
   auto* rf = new RecordFile();
   rf->fd = open(path, O_RDONLY);
@@ -315,6 +455,13 @@ RecordFile* open_file(const char* path, Kind kind) {
   if (m == MAP_FAILED) { close(rf->fd); delete rf; return nullptr; }
   rf->map = (const uint8_t*)m;
   std::memcpy(&rf->h, rf->map, sizeof(Header));
+  if (kind == TEXT) {
+    if (open_text(rf)) return rf;
+    munmap(m, rf->size);
+    close(rf->fd);
+    delete rf;
+    return nullptr;
+  }
   const uint64_t need = sizeof(Header) + rf->h.count * rf->h.record_bytes;
   const uint64_t ib = (uint64_t)rf->h.H * rf->h.W * rf->h.C;
   bool ok;
@@ -344,7 +491,7 @@ RecordFile* open_file(const char* path, Kind kind) {
 
 Loader* create_loader(void* file, Kind kind, int batch, int out_h, int out_w, int train, double smin, double smax,
                       double rmin, double rmax, uint64_t seed, int rank, int world, int shuffle, int drop_last,
-                      int threads, int chunk, int clip_len = 0, int frame_stride = 1) {
+                      int threads, int chunk, int clip_len = 0, int frame_stride = 1, int max_tokens = 0) {
   if (!file || batch <= 0 || world <= 0 || rank < 0 || rank >= world || threads <= 0) return nullptr;
   if (((const RecordFile*)file)->what() != kind) return nullptr;   // another kind of file
   if (kind == CLIP) {   // the clip's span (T-1)*s + 1 has to fit into the record's F frames
@@ -356,6 +503,7 @@ Loader* create_loader(void* file, Kind kind, int batch, int out_h, int out_w, in
   L->seg = kind == SEG;
   L->clip = kind == CLIP;
   L->clip_len = clip_len; L->frame_stride = frame_stride;
+  L->text = kind == TEXT; L->max_tokens = max_tokens;
   L->batch = batch; L->out_h = out_h; L->out_w = out_w; L->train = train;
   L->smin = smin; L->smax = smax; L->rmin = rmin; L->rmax = rmax;
   L->seed = seed; L->rank = rank; L->world = world; L->shuffle = shuffle; L->drop_last = drop_last;
@@ -461,6 +609,43 @@ MLR_EXPORT int mlr_clip_loader_set_slot(void* h, int i, uint8_t* img, int64_t* l
   return set_slot(L, i, img, lab, nullptr, par);
 }
 
+// a token record file; closed with mlr_close
+MLR_EXPORT void* mlr_text_open(const char* path) { return open_file(path, TEXT); }
+
+// shape[0..4] = count, longest record in tokens, vocab_size, token_bytes, total_tokens
+MLR_EXPORT void mlr_text_shape(void* h, uint64_t* shape) {
+  const auto* rf = (const RecordFile*)h;
+  shape[0] = rf->h.count; shape[1] = rf->h.H; shape[2] = rf->h.W; shape[3] = rf->h.C;
+  shape[4] = rf->total_tokens;
+}
+
+// the loader of an mlr_text_open file: batches of whole sequences, at most max_seqs of them
+// (1..1024) and max_tokens tokens; null when the file's longest record is over max_len (the
+// packer truncates, the loader does not) or max_len is over max_tokens; start_epoch / next /
+// release / destroy are the mlr_loader_* ones
+MLR_EXPORT void* mlr_text_loader_create(void* file, int max_tokens, int max_seqs, int max_len, int train,
+                                        uint64_t seed, int rank, int world, int shuffle, int threads, int chunk) {
+  if (!file || ((const RecordFile*)file)->what() != TEXT) return nullptr;
+  if (max_seqs < 1 || max_seqs > 1024 || max_len < 1 || max_len > max_tokens ||
+      ((const RecordFile*)file)->h.H > (uint32_t)max_len)
+    return nullptr;
+  Loader* L = create_loader(file, TEXT, max_seqs, 0, 0, train, 0, 0, 0, 0, seed, rank, world, shuffle, 0, threads,
+                            chunk, 0, 1, max_tokens);
+  return L;
+}
+
+// slot `i`: one int32 buffer of ((2 + 3*max_seqs + max_tokens + 1) & ~1) + 2*max_seqs ints,
+// 8-byte aligned (layout: the file comment)
+MLR_EXPORT int mlr_text_loader_set_slot(void* h, int i, int32_t* buf) {
+  auto* L = (Loader*)h;
+  if (!L->text) return -1;
+  std::lock_guard<std::mutex> lk(L->mu);
+  if (L->started || i < 0) return -1;
+  if ((int)L->slots.size() <= i) L->slots.resize((size_t)i + 1);
+  L->slots[(size_t)i].txt = buf;
+  return 0;
+}
+
 // (re)start at `epoch`; returns the number of batches this rank yields in it
 MLR_EXPORT int64_t mlr_loader_start_epoch(void* h, uint64_t epoch) {
   auto* L = (Loader*)h;
@@ -468,7 +653,7 @@ MLR_EXPORT int64_t mlr_loader_start_epoch(void* h, uint64_t epoch) {
     std::lock_guard<std::mutex> lk(L->mu);
     if (L->slots.empty()) return -1;
     for (auto& s : L->slots)
-      if (!s.img || !(L->seg ? (void*)s.mask : (void*)s.lab) || !s.par) return -1;
+      if (L->text ? !s.txt : (!s.img || !(L->seg ? (void*)s.mask : (void*)s.lab) || !s.par)) return -1;
   }
   L->start_epoch(epoch);
   return L->nbatches;

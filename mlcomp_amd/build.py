@@ -12,8 +12,8 @@
 * ``libmlcomp_runtime.so`` - host-side C++ runtime (``csrc/runtime``): the memory-mapped
   record files and the threaded batch gatherer of the native input pipeline
   (:mod:`mlcomp_amd.train.records`); ``mlcomp-records-selftest-<san>``,
-  ``mlcomp-records-seg-selftest-<san>`` and ``mlcomp-records-clip-selftest-<san>`` are its
-  ThreadSanitizer / AddressSanitizer self-tests.
+  ``mlcomp-records-seg-selftest-<san>``, ``mlcomp-records-clip-selftest-<san>`` and
+  ``mlcomp-records-text-selftest-<san>`` are its ThreadSanitizer / AddressSanitizer self-tests.
 
 Outputs live under ``mlcomp_amd/_native/`` so they travel with the repo snapshot.
 Compilation is incremental (mtime based) and parallel.
@@ -144,7 +144,8 @@ def build_runtime(verbose=False):
 
 def build_runtime_selftest(sanitize='tsan', verbose=False, main='records_selftest.cpp'):
     """A record loader self-test driver (``main``, a file of ``csrc/runtime``:
-    ``records_selftest.cpp``, ``records_seg_selftest.cpp`` or ``records_clip_selftest.cpp``) linked with an instrumented
+    ``records_selftest.cpp``, ``records_seg_selftest.cpp``, ``records_clip_selftest.cpp`` or
+    ``records_text_selftest.cpp``) linked with an instrumented
     copy of the runtime sources (``tsan``: ThreadSanitizer, ``asan``: AddressSanitizer +
     UBSan)."""
     os.makedirs(OUT, exist_ok=True)

@@ -174,5 +174,33 @@ def pack_clip_records(video_path, out, frames, size, frame_step, pad_short, fold
     click.echo(f'{n} clips of {frames} frames, {len(names)} classes -> {out}')
 
 
+@main.command('pack-text-records')
+@click.option('--csv', 'csv_path', required=True, help='the CSV with the text and label columns')
+@click.option('--text-col', default='text', help='column of the (first) text')
+@click.option('--text-b-col', default=None, help='column of the second text of a pair')
+@click.option('--label-col', default='label')
+@click.option('--vocab', required=True, help='the BERT vocab.txt the model was trained with')
+@click.option('--out', required=True, help='the text record file to write')
+@click.option('--max-len', type=int, default=128, help='longest record in tokens, [CLS] / [SEP] included')
+@click.option('--cased', is_flag=True, help='keep case and accents (the cased models)')
+@click.option('--fold-csv', default=None, help='fold.csv (a fold column, rows as in --csv): pack the rows of --fold only')
+@click.option('--fold', type=int, default=None)
+@click.option('--exclude-fold', is_flag=True, help='pack every fold except --fold (the training split)')
+def pack_text_records(csv_path, text_col, text_b_col, label_col, vocab, out, max_len, cased, fold_csv, fold,
+                      exclude_fold):
+    """Tokenise a CSV with WordPiece over --vocab and pack it into a text record file for the
+    native input pipeline (mlcomp_amd.train.records): [CLS] a [SEP] (b [SEP]) per row."""
+    from mlcomp_amd.train.records import pack_text_csv
+    try:
+        n, names = pack_text_csv(csv_path, vocab, out, text_col=text_col, label_col=label_col,
+                                 text_b_col=text_b_col, max_len=max_len, lower=not cased, fold_csv=fold_csv,
+                                 fold=fold, exclude_fold=exclude_fold)
+    except ValueError as e:
+        raise click.ClickException(str(e))
+    with open(out + '.classes', 'w') as f:
+        f.write('\n'.join(names) + '\n')
+    click.echo(f'{n} sequences, {len(names)} classes -> {out}')
+
+
 if __name__ == '__main__':
     main()

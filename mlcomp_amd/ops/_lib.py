@@ -52,6 +52,7 @@ _SIGS = {
     'mlc_augment': [vp, vp, vp, vp] + [i32] * 7 + [vp],
     'mlc_augment_seg': [vp] * 6 + [i32] * 9 + [vp],
     'mlc_augment_clip': [vp, vp, vp, vp] + [i32] * 8 + [vp],
+    'mlc_text_unpack': [vp, i32] + [vp] * 7 + [i32] * 5 + [vp],
     'mlc_gemm_bf16_ex': [vp, vp, vp] + [i32] * 8 + [vp, i32, vp, vp, vp, vp, i64, vp],
     'mlc_gemm_bf16_ex_native': [vp, vp, vp] + [i32] * 8 + [vp, i32, vp, vp, vp, vp, i64, vp],
     'mlc_ln_fwd': [vp] * 8 + [i32, i32, f32, f32, f32, vp, u32, u32, vp],

@@ -185,6 +185,26 @@ class NativeBertStep(GraphedStep):
             dst.copy_(src.to(self.device, non_blocking=True))
         self.nseq = nreal
 
+    def load_text_batch(self, pb):
+        """A batch staged by ``TextRecordLoader(layout='packed')`` (a ``PackedTextBatch``): one
+        kernel writes the step's six static buffers from the staged slot, so it works before
+        and after graph capture and nothing is packed on the host.  The batch must have been
+        built for this step's token rows, slots and longest sequence."""
+        if not self.packed:
+            raise RuntimeError('load_text_batch needs a step built with pack_tokens')
+        T, nmax = self.net.T, self.batch
+        if (pb.T, pb.nmax, pb.max_len) != (T, nmax, self.seq_len):
+            raise ValueError(f'the text batch was built for {pb.T} token rows, {pb.nmax} sequences of up to '
+                             f'{pb.max_len} tokens; this step holds {T}, {nmax} and {self.seq_len}')
+        c = self.net.c
+        if pb.vocab > c.vocab_size or pb.num_labels > c.num_labels:
+            raise ValueError(f'the text batch allows token ids below {pb.vocab} and labels below {pb.num_labels}; '
+                             f'the model has vocab_size = {c.vocab_size} and {c.num_labels} labels')
+        if pb.nseq < 1:
+            raise ValueError('a packed batch needs at least one sequence')
+        pb.unpack_into(self.ids, self.tt, self.net.pos_ids, self.net.cu, self.y, self.net.slot_w)
+        self.nseq = pb.nseq
+
     def load_batch(self, ids, labels, token_type_ids=None, attention_mask=None):
         self._check_ids(ids)
         if self.packed:

@@ -29,6 +29,12 @@ split between the host and the GPU instead.
   frames ``t0 + k*frame_stride`` into the slot, and one kernel (``mlc_augment_clip``)
   applies the transform to every frame and writes NCTHW fp32 or channels_last_3d bf16.
   :func:`augment_clip_reference` is its PyTorch twin.
+* Text: ``MLTXT001`` files hold token sequences of different lengths behind an index
+  (:func:`write_text_records`, :func:`pack_text_csv`, :class:`TextRecordFile`).
+  :class:`TextRecordLoader` plans token-budget batches in C++ (the rule of
+  ``TokenBudgetBatchSampler``), gathers each into one pinned int32 slot that crosses PCIe in
+  one copy, and one kernel (``mlc_text_unpack``) writes every tensor the packed or padded
+  BERT step reads.  :func:`text_unpack_reference` is its PyTorch twin.
 """
 from __future__ import annotations
 
@@ -50,6 +56,11 @@ SEG_HEADER = struct.Struct('<8s4I2Q2I16x')   # ... count, record_bytes, K, kind
 MASK_KINDS = {'planes': 0, 'index': 1}
 CLIP_MAGIC = b'MLVID001'
 CLIP_HEADER = struct.Struct('<8s4I2QI20x')   # ... count, record_bytes, F (frames per record)
+TEXT_MAGIC = b'MLTXT001'
+TEXT_HEADER = struct.Struct('<8s4I2QQ16x')   # ... count, record_bytes (0), total_tokens
+TEXT_ENTRY = np.dtype([('token_offset', '<u8'), ('length', '<u4'), ('type0_length', '<u4'), ('label', '<i4'),
+                       ('zero', '<u4')])
+TEXT_LAYOUTS = {'packed': 0, 'padded': 1}
 LAYOUTS = {'s2d': 0, 'nhwc8': 1, 'nchw': 2}
 CLIP_LAYOUTS = {'ncthw': 0, 'nthwc': 1}
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
@@ -346,6 +357,160 @@ class ClipRecordFile:
         return int(np.asarray(self._m[i, -4:]).view('<i4')[0])
 
 
+def write_text_records(path: str, sequences: Iterable, labels: Iterable[int], token_types: Optional[Iterable] = None,
+                       vocab_size: Optional[int] = None, type0_lengths: Optional[Iterable[int]] = None) -> int:
+    """Write token ``sequences`` (rows of ids in ``[0, vocab_size)``, at least one token each)
+    and their int labels to a text record file; returns the record count.  Token types come
+    as ``token_types`` (one row per sequence: zeros, then ones - anything else is refused) or
+    as ``type0_lengths`` (how many leading tokens of each sequence have type 0); neither:
+    all type 0.  Tokens are stored as u16 when the vocabulary fits, else u32.  Written to
+    ``path + '.tmp'`` and renamed; the tmp file is removed on error."""
+    if vocab_size is None or int(vocab_size) < 1:
+        raise ValueError('write_text_records needs the vocab_size the ids were made for')
+    vocab_size = int(vocab_size)
+    if token_types is not None and type0_lengths is not None:
+        raise ValueError('token_types or type0_lengths, not both')
+    types = iter(token_types) if token_types is not None else None
+    t0s = iter(type0_lengths) if type0_lengths is not None else None
+    labs = iter(labels)
+    rows, entries, off = [], [], 0
+    for n, seq in enumerate(sequences):
+        a = np.asarray(seq, dtype=np.int64).reshape(-1)
+        if a.size < 1:
+            raise ValueError(f'record {n}: an empty sequence')
+        if int(a.min()) < 0 or int(a.max()) >= vocab_size:
+            raise ValueError(f'record {n}: token ids must be in [0, {vocab_size}) '
+                             f'(got [{int(a.min())}, {int(a.max())}])')
+        t0 = a.size
+        if types is not None:
+            t = np.asarray(next(types), dtype=np.int64).reshape(-1)
+            t0 = int((t == 0).sum())
+            if t.size != a.size or not np.array_equal(t, (np.arange(a.size) >= t0).astype(np.int64)):
+                raise ValueError(f'record {n}: token types must be zeros followed by ones, one per token')
+        elif t0s is not None:
+            t0 = int(next(t0s))
+            if not 0 <= t0 <= a.size:
+                raise ValueError(f'record {n}: type0_length {t0} outside [0, {a.size}]')
+        try:
+            lab = int(next(labs))
+        except StopIteration:
+            raise ValueError(f'record {n}: more sequences than labels') from None
+        rows.append(a)
+        entries.append((off, a.size, t0, lab, 0))
+        off += a.size
+    if not rows:
+        raise ValueError('no records')
+    tb = 2 if vocab_size <= 65536 else 4
+    index = np.array(entries, dtype=TEXT_ENTRY)
+    tmp = path + '.tmp'
+    try:
+        with open(tmp, 'wb') as f:
+            f.write(TEXT_HEADER.pack(TEXT_MAGIC, int(index['length'].max()), vocab_size, tb, 4, len(rows), 0, off))
+            f.write(index.tobytes())
+            f.write(np.concatenate(rows).astype('<u2' if tb == 2 else '<u4').tobytes())
+    except BaseException:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        raise
+    os.replace(tmp, path)
+    return len(rows)
+
+
+class TextRecordFile:
+    """numpy view of a text record file (the python twin of ``mlr_text_open``, with its
+    checks) and a map-style dataset: item i is the dict ``SyntheticTextClassification`` gives,
+    right-padded to ``seq_len`` (default: the file's longest record; a shorter ``seq_len`` is
+    refused, truncation happens at pack time)."""
+
+    def __init__(self, path: str, seq_len: Optional[int] = None):
+        size = os.path.getsize(path)
+        with open(path, 'rb') as f:
+            raw = f.read(TEXT_HEADER.size)
+        bad = ValueError(f'{path}: not a text record file')
+        if len(raw) < TEXT_HEADER.size:
+            raise bad
+        magic, H, V, tb, lb, n, rb, total = TEXT_HEADER.unpack(raw)
+        if magic != TEXT_MAGIC or n < 1 or lb != 4 or rb != 0 or H < 1 or V < 1 \
+                or not (tb == 4 or (tb == 2 and V <= 65536)):
+            raise bad
+        if size < TEXT_HEADER.size + n * TEXT_ENTRY.itemsize + total * tb:
+            raise bad
+        self.index = np.memmap(path, dtype=TEXT_ENTRY, mode='r', offset=TEXT_HEADER.size, shape=(n,))
+        ln, off = self.index['length'].astype(np.int64), self.index['token_offset']
+        if int(ln.min()) < 1 or int(ln.max()) > H or bool((self.index['type0_length'] > ln).any()) \
+                or int(off.max()) > total or bool((ln > total - off.astype(np.int64)).any()):
+            raise bad
+        self.count, self.max_len, self.vocab_size, self.token_bytes, self.total_tokens = n, H, V, tb, total
+        self.seq_len = H if seq_len is None else int(seq_len)
+        if self.seq_len < H:
+            raise ValueError(f'{path}: seq_len {self.seq_len} is shorter than the longest record ({H} tokens)')
+        self._tok = np.memmap(path, dtype='<u2' if tb == 2 else '<u4', mode='r',
+                              offset=TEXT_HEADER.size + n * TEXT_ENTRY.itemsize, shape=(total,))
+
+    def __len__(self):
+        return self.count
+
+    def lengths(self):
+        return self.index['length'].tolist()
+
+    def tokens(self, i: int) -> np.ndarray:
+        e = self.index[i]
+        return np.asarray(self._tok[int(e['token_offset']):int(e['token_offset']) + int(e['length'])]).astype(np.int64)
+
+    def label(self, i: int) -> int:
+        return int(self.index[i]['label'])
+
+    def type0_length(self, i: int) -> int:
+        return int(self.index[i]['type0_length'])
+
+    def __getitem__(self, i: int):
+        t = self.tokens(i)
+        S, n = self.seq_len, t.size
+        ids = torch.zeros(S, dtype=torch.long)
+        ids[:n] = torch.from_numpy(t)
+        pos = torch.arange(S)
+        mask = (pos < n).long()
+        return {'input_ids': ids, 'token_type_ids': (pos >= self.type0_length(i)).long() * mask,
+                'attention_mask': mask, 'targets': self.label(i)}
+
+
+def pack_text_csv(csv_path: str, vocab_path: str, out: str, text_col: str = 'text', label_col: str = 'label',
+                  text_b_col: Optional[str] = None, max_len: int = 128, lower: bool = True,
+                  fold_csv: Optional[str] = None, fold: Optional[int] = None, exclude_fold: bool = False):
+    """Tokenise the rows of a CSV with :class:`~mlcomp_amd.train.tokenizer.WordPieceTokenizer`
+    (``[CLS] a [SEP]`` or, with ``text_b_col``, ``[CLS] a [SEP] b [SEP]``, truncated to
+    ``max_len``) and write a text record file.  Labels are the sorted distinct values of
+    ``label_col``; returns ``(records, label names)``.  ``fold_csv`` (a ``fold`` column, rows
+    aligned with the CSV's) keeps the rows of ``fold`` only, or every other fold with
+    ``exclude_fold``."""
+    import pandas as pd
+    from .tokenizer import WordPieceTokenizer
+    df = pd.read_csv(csv_path)
+    for col in (text_col, label_col) + ((text_b_col,) if text_b_col else ()):
+        if col not in df.columns:
+            raise ValueError(f'{csv_path}: no column {col!r} (has {", ".join(map(str, df.columns))})')
+    names = sorted(df[label_col].astype(str).unique())
+    if fold_csv:
+        folds = pd.read_csv(fold_csv)
+        if len(folds) != len(df) or 'fold' not in folds.columns:
+            raise ValueError(f'{fold_csv}: needs a fold column with one row per row of {csv_path}')
+        if fold is not None:
+            keep = (folds['fold'] != fold) if exclude_fold else (folds['fold'] == fold)
+            df = df[keep.values]
+    elif fold is not None and 'fold' in df.columns:
+        df = df[(df['fold'] != fold) if exclude_fold else (df['fold'] == fold)]
+    tok = WordPieceTokenizer(vocab_path, lower=lower)
+    seqs, t0s, labels = [], [], []
+    for _, row in df.iterrows():
+        b = None if not text_b_col or pd.isna(row[text_b_col]) else str(row[text_b_col])
+        ids, t0 = tok.encode('' if pd.isna(row[text_col]) else str(row[text_col]), b, max_len=max_len)
+        seqs.append(ids)
+        t0s.append(t0)
+        labels.append(names.index(str(row[label_col])))
+    n = write_text_records(out, seqs, labels, type0_lengths=t0s, vocab_size=len(tok.vocab))
+    return n, names
+
+
 # ------------------------------------------------------------------------- runtime
 _RT = None
 
@@ -375,6 +540,9 @@ def runtime():
         'mlr_clip_loader_create': ([vp, i32, i32, i32, i32, i32, i32, f64, f64, f64, f64, u64, i32, i32, i32, i32,
                                     i32, i32], vp),
         'mlr_clip_loader_set_slot': ([vp, i32, vp, vp, vp], i32),
+        'mlr_text_open': ([C.c_char_p], vp), 'mlr_text_shape': ([vp, vp], None),
+        'mlr_text_loader_create': ([vp, i32, i32, i32, i32, u64, i32, i32, i32, i32, i32], vp),
+        'mlr_text_loader_set_slot': ([vp, i32, vp], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -859,7 +1027,294 @@ class ClipRecordLoader(RecordLoader):
         return out, dlab, done
 
 
+# ------------------------------------------------------------------------- text
+def text_slot_ints(max_tokens: int, max_seqs: int) -> Tuple[int, int]:
+    """(ints that cross to the device, ints of the whole slot) of a text loader slot:
+    ``{nseq, total}``, ``{length, type0_length, label}[max_seqs]``, ``tokens[max_tokens]``, then
+    - 8-byte aligned, host only - ``int64 indices[max_seqs]``."""
+    head = 2 + 3 * max_seqs + max_tokens
+    return head, ((head + 1) & ~1) + 2 * max_seqs
+
+
+def text_unpack_reference(slot: torch.Tensor, T: int, nmax: int, max_len: int, vocab: int, num_labels: int,
+                          layout: str = 'packed'):
+    """PyTorch twin of ``mlc_text_unpack``: the int32 ``slot`` a text loader staged ->
+    ``(tensors, err)``.  ``packed``: ``ids`` / ``tt`` / ``pos_ids`` int64 [T], ``cu`` int32
+    [nmax + 1], ``y`` int64 [nmax], ``slot_w`` f32 [nmax]; ``padded``: ``input_ids`` /
+    ``token_type_ids`` / ``attention_mask`` int64 [nmax, max_len] and ``y``.  The clamps are
+    the kernel's (``csrc/kernels/text.hip``) and ``err`` counts them as its counter does."""
+    if layout not in TEXT_LAYOUTS:
+        raise ValueError(f'text layout: {" / ".join(TEXT_LAYOUTS)}, not {layout!r}')
+    s = slot.detach().cpu().to(torch.int64)
+    nseq = min(max(int(s[0]), 0), nmax)
+    err = int(nseq != int(s[0]))
+    ent = s[2:2 + 3 * nmax].view(nmax, 3)[:nseq]
+    tok = s[2 + 3 * nmax:2 + 3 * nmax + T]
+    cu = torch.zeros(nseq + 1, dtype=torch.int64)
+    cu[1:] = torch.cumsum(ent[:, 0].clamp(0, max_len), 0).clamp(max=T)
+    lens = cu[1:] - cu[:-1]
+    total = int(cu[-1])
+    err += int((lens != ent[:, 0]).sum()) + int(int(s[1]) != total)
+    t0 = torch.minimum(ent[:, 1].clamp(min=0), lens)
+    lab = ent[:, 2].clamp(0, num_labels - 1)
+    err += int((t0 != ent[:, 1]).sum()) + int((lab != ent[:, 2]).sum())
+    seq = torch.repeat_interleave(torch.arange(nseq), lens)
+    q = torch.arange(total) - cu[:-1][seq]
+    ids = tok[:total].clamp(0, vocab - 1)
+    err += int((ids != tok[:total]).sum())
+    tt = (q >= t0[seq]).long()
+    y = torch.zeros(nmax, dtype=torch.long)
+    y[:nseq] = lab
+    if layout == 'padded':
+        out = {k: torch.zeros(nmax, max_len, dtype=torch.long)
+               for k in ('input_ids', 'token_type_ids', 'attention_mask')}
+        out['input_ids'][seq, q] = ids
+        out['token_type_ids'][seq, q] = tt
+        out['attention_mask'][seq, q] = 1
+        out['y'] = y
+        return out, err
+    out = {k: torch.zeros(T, dtype=torch.long) for k in ('ids', 'tt', 'pos_ids')}
+    out['ids'][:total] = ids
+    out['tt'][:total] = tt
+    out['pos_ids'][:total] = q
+    out['cu'] = torch.full((nmax + 1,), total, dtype=torch.int32)
+    out['cu'][:nseq + 1] = cu.to(torch.int32)
+    out['y'] = y
+    nreal = int((lens > 0).sum())
+    out['slot_w'] = torch.zeros(nmax, dtype=torch.float32)
+    if nreal:
+        out['slot_w'][:nseq] = (lens > 0).float() / nreal
+    return out, err
+
+
+class PackedTextBatch:
+    """One batch a :class:`TextRecordLoader` staged, not yet unpacked: ``nseq`` sequences of
+    ``tokens`` tokens in all (host ints), built for a step of ``T`` token rows, ``nmax``
+    slots and sequences up to ``max_len``.  :meth:`unpack_into` writes the six tensors a
+    packed ``NativeBertStep`` reads into the caller's buffers, with one kernel launch on the
+    current stream; :meth:`tensors` allocates them."""
+
+    def __init__(self, loader, staged, done, nseq, tokens):
+        self._loader, self._staged, self._done = loader, staged, done
+        self.nseq, self.tokens = int(nseq), int(tokens)
+        self.T, self.nmax, self.max_len = loader.T, loader.max_seqs, loader.max_len
+        self.vocab, self.num_labels = loader.vocab_size, loader.num_labels
+
+    def unpack_into(self, ids, tt, pos_ids, cu, y, slot_w):
+        outs = (ids, tt, pos_ids, cu, y, slot_w)
+        want = ((self.T, torch.int64),) * 3 + ((self.nmax + 1, torch.int32), (self.nmax, torch.int64),
+                                               (self.nmax, torch.float32))
+        for t, (n, dt) in zip(outs, want):
+            if t.numel() != n or t.dtype != dt or not t.is_contiguous() or t.device != self._staged.device:
+                raise ValueError(f'unpack_into: a contiguous {dt} buffer of {n} elements on '
+                                 f'{self._staged.device} expected, got {tuple(t.shape)} {t.dtype} on {t.device}')
+        self._loader._unpack(self._staged, self._done, 'packed', outs)
+
+    def tensors(self):
+        dev = self._staged.device
+        z = lambda n, dt: torch.empty(n, dtype=dt, device=dev)  # noqa: E731
+        out = {'ids': z(self.T, torch.int64), 'tt': z(self.T, torch.int64), 'pos_ids': z(self.T, torch.int64),
+               'cu': z(self.nmax + 1, torch.int32), 'y': z(self.nmax, torch.int64),
+               'slot_w': z(self.nmax, torch.float32)}
+        self.unpack_into(*out.values())
+        return out
+
+
+class TextRecordLoader(RecordLoader):
+    """Batches of a text record file, on the slot ring and copy stream of :class:`RecordLoader`.
+
+    A batch holds whole sequences: at most ``batch_size`` of them and ``pack_tokens`` tokens
+    (default ``batch_size * max_len``: plain batches of ``batch_size``), filled greedily in
+    the epoch's order by the rule of ``TokenBudgetBatchSampler``; the C++ runtime plans the
+    epoch.  ``train`` shuffles per epoch and, with ``world_size > 1``, runs every rank for
+    the step count of the rank with the fewest; otherwise file order and all of the rank's
+    batches.  The file's longest record must fit ``max_len`` (truncate when packing).
+
+    ``layout='padded'`` yields ``{'input_ids', 'token_type_ids', 'attention_mask',
+    'targets'}`` on ``device``, ``[n, max_len]`` for the batch's n sequences, and
+    ``'indices'`` (the record numbers, on the host).  ``layout='packed'`` yields ``{'packed':
+    PackedTextBatch, 'targets', 'indices'}`` (both on the host) for
+    ``NativeBertStep.load_text_batch``.  ``vocab_size`` is the model's: a file with a larger
+    vocabulary is refused.  Token ids or labels out of range never reach the model: the
+    unpack kernel clamps them and counts; :meth:`bad_tokens` reads the count, and the iterator
+    raises ``ValueError`` at the end of an epoch that had any.  ``drop_last`` (plain batches
+    only) skips a last batch of fewer than ``batch_size`` sequences, for engines of a fixed
+    batch shape."""
+
+    def __init__(self, path: str, batch_size: int, max_len: int = 128, pack_tokens: Optional[int] = None,
+                 train: bool = True, layout: str = 'packed', vocab_size: Optional[int] = None, num_labels: int = 2,
+                 seed: int = 0, rank: int = 0, world_size: int = 1, shuffle: Optional[bool] = None,
+                 threads: int = 4, depth: int = 4, device=None, chunk: int = 16, drop_last: bool = False):
+        if layout not in TEXT_LAYOUTS:
+            raise ValueError(f'text layout: {" / ".join(TEXT_LAYOUTS)}, not {layout!r}')
+        if drop_last and pack_tokens is not None:
+            raise ValueError('drop_last is for plain batches (pack_tokens=None): a token-budget batch has no full size')
+        self.drop_last = bool(drop_last)
+        self.path, self.layout, self.train = path, layout, bool(train)
+        self.batch_size = self.max_seqs = int(batch_size)
+        self.max_len = int(max_len)
+        self.max_tokens = int(pack_tokens) if pack_tokens is not None else self.max_seqs * self.max_len
+        self.T = (self.max_tokens + 7) // 8 * 8          # token rows of the device tensors
+        self.num_labels = int(num_labels)
+        self.device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
+        self.epoch = 0
+        self._explicit_epoch = False
+        self._live = None
+        self._planned = None                              # (epoch, steps) the runtime has started
+        rt = self._rt = runtime()
+        self._file = rt.mlr_text_open(path.encode())
+        if not self._file:
+            raise ValueError(f'{path}: cannot open text record file')
+        shp = (C.c_uint64 * 5)()
+        rt.mlr_text_shape(self._file, shp)
+        self.count, self.file_max_len, self.file_vocab, self.token_bytes, self.total_tokens = (int(v) for v in shp)
+        if vocab_size is not None and self.file_vocab > int(vocab_size):
+            raise ValueError(f'{path}: the file was packed with a vocabulary of {self.file_vocab} tokens, the '
+                             f'model has vocab_size = {int(vocab_size)}')
+        self.vocab_size = int(vocab_size) if vocab_size is not None else self.file_vocab
+        if not 1 <= self.max_seqs <= 1024:
+            raise ValueError(f'batch_size {self.max_seqs}: 1 .. 1024 sequences per batch')
+        if self.file_max_len > self.max_len:
+            raise ValueError(f'{path}: the longest record has {self.file_max_len} tokens, over max_len = '
+                             f'{self.max_len} (pack with --max-len {self.max_len})')
+        if self.max_len > self.max_tokens or (layout == 'packed' and self.max_tokens % 8):
+            raise ValueError(f'pack_tokens {self.max_tokens}: at least max_len = {self.max_len}'
+                             + (', a multiple of 8' if layout == 'packed' else ''))
+        shuffle = self.train if shuffle is None else shuffle
+        self._rank, self._world = int(rank), int(world_size)
+        self._loader = rt.mlr_text_loader_create(self._file, self.max_tokens, self.max_seqs, self.max_len,
+                                                 int(self.train), int(seed), int(rank), int(world_size),
+                                                 int(shuffle), int(threads), int(chunk))
+        if not self._loader:
+            raise ValueError('bad loader arguments')
+        cuda = self.device.type == 'cuda'
+        self._head, ints = text_slot_ints(self.max_tokens, self.max_seqs)
+        self._slots = []
+        for i in range(max(3, int(depth))):
+            buf = torch.zeros(ints, dtype=torch.int32, pin_memory=cuda)
+            rt.mlr_text_loader_set_slot(self._loader, i, C.c_void_p(buf.data_ptr()))
+            self._slots.append(buf)
+        self._err = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._err_cpu = 0
+        if cuda:
+            self._copy_stream = torch.cuda.Stream(self.device)
+
+    def _start(self):
+        """Plan and start ``self.epoch`` in the runtime (once: ``len()`` before the epoch's
+        iterator starts it early, and the workers prefetch from then on)."""
+        if self._planned is None or self._planned[0] != self.epoch:
+            n = self._rt.mlr_loader_start_epoch(self._loader, self.epoch)
+            if n < 0:
+                raise RuntimeError('record loader: slots not registered')
+            self._planned = (self.epoch, int(n))
+        return self._planned[1]
+
+    def _short_last(self, steps):
+        """Whether the last of ``steps`` plain batches is short and ``drop_last`` drops it: the
+        rank holds every world-th record, ``batch_size`` to a batch."""
+        own = len(range(self._rank, self.count, self._world))
+        return self.drop_last and steps > 0 and steps * self.max_seqs > own
+
+    def __len__(self):
+        live = self._live() if self._live is not None else None
+        if live is not None and self._planned is not None and live.gi_frame is not None:
+            n = self._planned[1]                          # mid-epoch: the running epoch's plan
+        else:
+            n = self._start()
+        return n - int(self._short_last(n))
+
+    def bad_tokens(self) -> int:
+        """Clamps the unpack kernel had to apply since the last check (a sync point)."""
+        return int(self._err.item()) if self.device.type == 'cuda' else self._err_cpu
+
+    def _unpack(self, staged, done, layout, outs):
+        nmax, T = self.max_seqs, self.T
+        if self.device.type != 'cuda':
+            ref, err = text_unpack_reference(staged, T, nmax, self.max_len, self.vocab_size, self.num_labels, layout)
+            for dst, src in zip(outs, ref.values()):
+                dst.view(src.shape).copy_(src)
+            self._err_cpu += err
+            return
+        from mlcomp_amd.ops import _lib
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(done)
+        staged.record_stream(cur)       # its memory goes back to the copy stream's pool after this launch
+        if layout == 'packed':
+            ids, tt, pos, cu, y, w = outs
+        else:
+            (ids, tt, pos, y), cu, w = outs, None, None
+        _lib.call('mlc_text_unpack', _lib.ptr(staged), TEXT_LAYOUTS[layout], _lib.ptr(ids), _lib.ptr(tt),
+                  _lib.ptr(pos), _lib.ptr(cu), _lib.ptr(y), _lib.ptr(w), _lib.ptr(self._err), T, nmax, self.max_len,
+                  self.vocab_size, self.num_labels, _lib.stream())
+
+    def _stage(self, buf):
+        """The device copy of a slot's head (its own tensor per batch, so a later batch's copy
+        never lands in memory an earlier batch's unpack has yet to read) and the copy's event."""
+        if self.device.type != 'cuda':
+            return buf[:self._head].clone(), None
+        with torch.cuda.stream(self._copy_stream):
+            staged = torch.empty(self._head, dtype=torch.int32, device=self.device)
+            staged.copy_(buf[:self._head], non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(self._copy_stream)
+        return staged, done
+
+    def _epoch_iter(self):
+        rt = self._rt
+        n = self._start()
+        nmax, head = self.max_seqs, self._head
+        ioff = (head + 1) & ~1
+        pending = None   # (slot index, copy-done event) of the previous batch
+        bi = C.c_int64(0)
+        try:
+            for k in range(n):
+                s = rt.mlr_loader_next(self._loader, C.byref(bi))
+                if s < 0:
+                    break
+                buf = self._slots[s]
+                nseq, total = int(buf[0]), int(buf[1])
+                if self.drop_last and nseq < nmax:
+                    rt.mlr_loader_release(self._loader, s)
+                    continue
+                indices = buf[ioff:ioff + 2 * nmax].view(torch.int64)[:nseq].clone()
+                targets = buf[2:2 + 3 * nmax].view(nmax, 3)[:nseq, 2].long()
+                staged, done = self._stage(buf)
+                if done is None:
+                    rt.mlr_loader_release(self._loader, s)
+                    s = -1
+                if pending is not None:   # the previous slot's copy is long done: hand it back
+                    pending[1].synchronize()
+                    rt.mlr_loader_release(self._loader, pending[0])
+                pending = (s, done) if s >= 0 else None
+                if self.layout == 'packed':
+                    yield {'packed': PackedTextBatch(self, staged, done, nseq, total), 'targets': targets,
+                           'indices': indices}
+                    continue
+                z = lambda: torch.empty(nmax, self.max_len, dtype=torch.long, device=self.device)  # noqa: E731
+                ids, tt, mask, y = z(), z(), z(), torch.empty(nmax, dtype=torch.long, device=self.device)
+                self._unpack(staged, done, 'padded', (ids, tt, mask, y))
+                yield {'input_ids': ids[:nseq], 'token_type_ids': tt[:nseq], 'attention_mask': mask[:nseq],
+                       'targets': y[:nseq], 'indices': indices}
+            bad = self.bad_tokens()
+            if bad:
+                self._err.zero_()
+                self._err_cpu = 0
+                raise ValueError(f'{self.path}: {bad} token ids / labels / lengths were out of range for '
+                                 f'vocab_size = {self.vocab_size}, num_labels = {self.num_labels}, max_len = '
+                                 f'{self.max_len} and were clamped')
+        finally:
+            if pending is not None:
+                pending[1].synchronize()
+                rt.mlr_loader_release(self._loader, pending[0])
+            self._planned = None
+            if not self._explicit_epoch:
+                self.epoch += 1
+            self._explicit_epoch = False
+
+
 __all__ = ['write_records', 'pack_images', 'RecordFile', 'RecordLoader', 'augment_reference', 'runtime',
            'write_seg_records', 'pack_seg_images', 'SegRecordFile', 'SegRecordLoader', 'augment_seg_reference',
            'write_clip_records', 'pack_clip_frames', 'ClipRecordFile', 'ClipRecordLoader', 'augment_clip_reference',
-           'CLIP_LAYOUTS']
+           'CLIP_LAYOUTS', 'TEXT_MAGIC', 'SEG_MAGIC', 'CLIP_MAGIC', 'write_text_records', 'pack_text_csv',
+           'TextRecordFile', 'TextRecordLoader', 'PackedTextBatch', 'text_unpack_reference', 'text_slot_ints',
+           'TEXT_LAYOUTS']

@@ -284,16 +284,19 @@ class Runner:
             return
         if self.native_kind == 'bert':
             from .native_bert_step import NativeBertStep
-            ids = batch['input_ids']
             self.model.to(self.device)
-            nseq = ids.shape[0]
+            if 'packed' in batch:   # a text record loader's staged batch says what it was built for
+                nseq, seq_len = batch['packed'].nseq, batch['packed'].max_len
+            else:
+                nseq, seq_len = batch['input_ids'].shape
+            have = nseq
             if self.pack_tokens is not None:
                 # packed mode: data_params.batch_size is the most sequences a step holds (the
                 # first batch may hold fewer), the row count is the token budget
                 plan['pack_tokens'] = self.pack_tokens
                 nseq = int(self.experiment.stage_params(self.state.stage, 'data_params').get('batch_size', 32))
             self.native_step = NativeBertStep(
-                torch_model=self.model, batch=max(nseq, ids.shape[0]), seq_len=ids.shape[1], device=self.device,
+                torch_model=self.model, batch=max(nseq, have), seq_len=seq_len, device=self.device,
                 world_size=self.world_size, num_labels=self.model.config.num_labels, use_graph=use_graph, **plan)
             self._apply_native_opt_state()
             return
@@ -384,13 +387,16 @@ class Runner:
         """``dataset: records``: the native input pipeline over ``path`` (train) and
         ``valid_path`` record files (:mod:`mlcomp_amd.train.records`); the native engine
         gets the stem's space-to-depth image straight from the augment kernel."""
-        from .records import CLIP_MAGIC, SEG_MAGIC, RecordLoader
+        from .records import CLIP_MAGIC, SEG_MAGIC, TEXT_MAGIC, RecordLoader
         try:
             with open(dp['path'], 'rb') as f:
                 magic = f.read(8)
         except OSError:     # the loader below reports a file it cannot open
             magic = b''
-        kind = dp.get('kind', {SEG_MAGIC: 'segmentation', CLIP_MAGIC: 'video'}.get(magic, 'classification'))
+        kind = dp.get('kind', {SEG_MAGIC: 'segmentation', CLIP_MAGIC: 'video', TEXT_MAGIC: 'text'}.get(
+            magic, 'classification'))
+        if kind == 'text':
+            return self._text_record_loaders(dp, bs)
         if kind == 'segmentation':
             return self._seg_record_loaders(dp, bs)
         if kind == 'video':
@@ -450,6 +456,32 @@ class Runner:
                                         ratio=tuple(dp.get('ratio', (3 / 4, 4 / 3))), **common)
         if dp.get('valid_path'):
             out['valid'] = ClipRecordLoader(dp['valid_path'], bs, train=False, **common)
+        return out
+
+    def _text_record_loaders(self, dp, bs) -> 'OrderedDict[str, object]':
+        """``dataset: records`` over text files (``kind: text``, or told from the file header).
+        A stage on the native BERT engine with ``args.pack_tokens`` gets packed batches
+        (``pack_tokens`` tokens, at most ``batch_size`` sequences of up to ``seq_len`` tokens)
+        that ``NativeBertStep.load_text_batch`` unpacks on the GPU; every other stage gets the
+        padded dicts the torch engine reads.  ``valid_path`` is always padded and in file
+        order.  A file packed with a larger vocabulary than the model's is refused here,
+        before anything runs on the GPU."""
+        from .records import TextRecordLoader
+        native = self.state.native and self.native_kind == 'bert'
+        packed = native and getattr(self, 'pack_tokens', None) is not None
+        cfg = getattr(self.model, 'config', None)
+        common = dict(max_len=int(dp.get('seq_len', 128)), rank=self.rank, world_size=self.world_size,
+                      threads=int(dp.get('num_workers', 4) or 4), device=self.device, seed=int(dp.get('seed', 0)),
+                      vocab_size=getattr(cfg, 'vocab_size', None),
+                      num_labels=int(getattr(cfg, 'num_labels', dp.get('num_classes', 2))))
+        out = OrderedDict()
+        if packed:
+            out['train'] = TextRecordLoader(dp['path'], bs, pack_tokens=self.pack_tokens, train=True,
+                                            layout='packed', **common)
+        else:   # the padded native engine has one batch shape: it drops a short last batch
+            out['train'] = TextRecordLoader(dp['path'], bs, train=True, layout='padded', drop_last=native, **common)
+        if dp.get('valid_path'):
+            out['valid'] = TextRecordLoader(dp['valid_path'], bs, train=False, layout='padded', **common)
         return out
 
     def _seg_stem_s2d(self) -> bool:
@@ -600,8 +632,11 @@ class Runner:
                     count += st.batch_size
                     continue
                 if self.native_kind == 'bert':
-                    ns.load_batch(batch['input_ids'], batch['targets'], batch.get('token_type_ids'),
-                                  batch.get('attention_mask'))
+                    if 'packed' in batch:   # staged by a text record loader: unpacked by one kernel
+                        ns.load_text_batch(batch['packed'])
+                    else:
+                        ns.load_batch(batch['input_ids'], batch['targets'], batch.get('token_type_ids'),
+                                      batch.get('attention_mask'))
                     head = ns.net
                 else:
                     ns.load_batch(batch['features'], batch['targets'])
