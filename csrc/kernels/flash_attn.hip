@@ -877,9 +877,318 @@ fwd128_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, 
   store_rows<NJ>(out + ((size_t)G.b * S + q) * E + G.hd * D, o, lane);
 }
 
+// ------------------------------------------------------------------ packed, max_len <= 128, D = 64
+// The whole-sequence form of the packed call: the S = 128 pair's one-launch structure, LDS
+// images and fragment reads, with the work cut to the sequence's length L.  Block (b, h) reads
+// its rows from cu_seqlens (seq_of<true>: start clamped to [0, T], length to max_len and to
+// the rows left) and only the nq = ceil(L / 32) 32-row groups below the length exist:
+// * staging stops after ceil(L / 64) 64-row images (rows past L in the last one re-read row
+//   L - 1, as Tile::load clamps), and nothing past them is read from LDS;
+// * a wave whose 32 rows start at or past L stages, synchronises and does nothing else;
+// * every loop over key / query groups (and phase B's 16-key steps) carries the wave-uniform
+//   guard `group < nq`, so the loops stay unrolled and the accumulators stay in registers;
+// * keys in [L, 32 nq) get -inf by index compare, queries there lse = +inf (backward), so
+//   their probabilities and dS are exact zeros and every dS column phase B reads is written;
+// * stores are guarded per lane by row < L: an attention block writes its sequence's rows only.
+// The grid is nseq_max * H attention blocks (XCD-remapped among themselves) followed by TAILB
+// tail blocks that zero the rows of no sequence, cu[nseq_max] .. T-1, with plain vector
+// stores, so the caller's buffers need no zero fill.  Host integers only: one captured graph
+// replays on any split.  Dropout index as the streaming packed kernels: ((b*H + h)*max_len +
+// q)*max_len + key.  No atomics.
+constexpr int TAILB = 16;
+// built without the packed fp32 VALU forms (v_pk_{add,mul,fma}_f32): scalar fp32 only
+#define VARLEN128_TARGET __attribute__((target("no-packed-fp32-ops")))
+
+// rows end .. T-1 of a [T][row_bytes] buffer (row_bytes % 16 == 0) as 16-byte zero vectors
+__device__ __forceinline__ void zero_tail_rows(void* buf, long row_bytes, int end, int T, int blk) {
+  uint4* p = reinterpret_cast<uint4*>(static_cast<char*>(buf) + (long)end * row_bytes);
+  const long n = (long)(T - end) * (row_bytes / 16);
+  const uint4 z = {0u, 0u, 0u, 0u};
+  for (long i = (long)blk * NT + threadIdx.x; i < n; i += (long)TAILB * NT) p[i] = z;
+}
+// first row of no sequence: cu[nseq_max] clamped to [0, T]
+__device__ __forceinline__ int tail_start(const VarLen& vl, int nseq) { return min(max(vl.cu[nseq], 0), vl.T); }
+
+template <bool DROP>
+__global__ void __launch_bounds__(NT) VARLEN128_TARGET
+fwd128_varlen_kernel(const bf16* __restrict__ qkv, VarLen vl, bf16* __restrict__ out, float* __restrict__ lse,
+                     int nseq, int max_len, int H, float sl2, uint32_t thr, float inv_keep,
+                     const uint32_t* __restrict__ seedp, uint32_t salt) {
+  constexpr int D = 64, NS = D / 16, NJ = D / 32, IMG = KT * D * 2;
+  __shared__ __attribute__((aligned(16))) char smem[4 * IMG];   // K (2 images) | V (2)
+  char* Ki = smem;
+  char* Vi = smem + 2 * IMG;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, hh = lane >> 5, l32 = lane & 31;
+  const int nattn = nseq * H, E = H * D, ld = 3 * E;
+  if ((int)blockIdx.x >= nattn) {   // tail block: out rows, and the H lse entries of each row
+    const int blk = blockIdx.x - nattn, end = tail_start(vl, nseq), nt = vl.T - end;
+    zero_tail_rows(out, (long)E * 2, end, vl.T, blk);
+    // lse [H][T]: row `end` of a head sits at any 4-byte offset, so these are 4-byte stores
+    for (int i = blk * NT + tid; i < H * nt; i += TAILB * NT) {
+      const int h = i / nt;
+      lse[(long)h * vl.T + end + (i - h * nt)] = 0.f;
+    }
+    return;
+  }
+  const int bh = xcd_remap(blockIdx.x, nattn), b = bh / H, hd = bh - b * H;
+  const Seq sq = seq_of<true>(b, hd, bh, max_len, vl);
+  const int L = sq.len;
+  if (L <= 0) return;   // an empty slot: before any barrier or LDS traffic (block-uniform)
+  const int nq = (L + 31) >> 5;
+  const bf16* Qg = qkv + (size_t)sq.row0 * ld + hd * D;
+  const bf16* Kg = Qg + E;
+  const bf16* Vg = Qg + 2 * E;
+  const int q = 32 * w + l32, qc = min(q, L - 1);
+  {
+    Tile<D> k0, v0;
+    k0.load(Kg, ld, tid, min(L, KT));
+    v0.load(Vg, ld, tid, min(L, KT));
+    if (L > KT) {   // the second image, fetched behind the first one's loads
+      Tile<D> k1, v1;
+      k1.load(Kg + (size_t)KT * ld, ld, tid, L - KT);
+      v1.load(Vg + (size_t)KT * ld, ld, tid, L - KT);
+      k1.store(Ki + IMG, tid);
+      v1.store(Vi + IMG, tid);
+    }
+    k0.store(Ki, tid);
+    v0.store(Vi, tid);
+  }
+  bf16x8 qf[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) qf[s] = gfrag(Qg, ld, qc, s, lane);
+  const uint32_t seed = seedp ? *seedp : 0u;
+  const uint32_t rowidx = ((uint32_t)bh * max_len + qc) * max_len;
+  __syncthreads();
+  if (32 * __builtin_amdgcn_readfirstlane(w) >= L) return;   // this wave's queries are all past the length
+  f32x16 a[4];
+  float m = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    if (i < nq) {
+      zero(a[i]);
+#pragma unroll
+      for (int s = 0; s < NS; ++s) a[i] = mfma(rowf<D>(Ki, 32 * i + l32, s, lane), qf[s], a[i]);
+      const bool part = 32 * i + 32 > L;   // the group that holds keys past the length
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        float x = a[i][r] * sl2;
+        if (part && 32 * i + acc_row(r, hh) >= L) x = -INFINITY;
+        a[i][r] = x;
+        m = fmaxf(m, x);
+      }
+    }
+  m = fmaxf(m, __shfl_xor(m, 32, 64));   // key 0 is always real: m is finite
+  float l = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    if (i < nq) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float e = __builtin_amdgcn_exp2f(a[i][r] - m);
+        l += e;
+        a[i][r] = e;
+      }
+      if constexpr (DROP) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          a[i][r] = keep(seed, salt, rowidx + 32 * i + acc_row(r, hh), thr) ? a[i][r] * inv_keep : 0.f;
+      }
+    }
+  f32x16 o[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) zero(o[j]);
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    if (i < nq) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const bf16x8 pb = acc_frag(a[i], s);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) o[j] = mfma(trf<D>(Vi, 32 * j, 32 * i + 16 * s, lane), pb, o[j]);
+      }
+    }
+  l += __shfl_xor(l, 32, 64);
+  const float inv = 1.f / l;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[j][r] *= inv;
+  if (q < L) {
+    if (hh == 0) lse[sq.stat0 + q] = (m + __log2f(l)) * LN2;
+    store_rows<NJ>(out + ((size_t)sq.row0 + q) * E + hd * D, o, lane);
+  }
+}
+
+// backward: bwd128_kernel's phase 0 / A / B with the same 81 KB of LDS (one block per CU)
+template <bool DROP>
+__global__ void __launch_bounds__(NT) VARLEN128_TARGET
+bwd128_varlen_kernel(const bf16* __restrict__ qkv, VarLen vl, const bf16* __restrict__ out,
+                     const bf16* __restrict__ dout, const float* __restrict__ lse, bf16* __restrict__ dqkv,
+                     int nseq, int max_len, int H, float scale, float sl2, uint32_t thr, float inv_keep,
+                     const uint32_t* __restrict__ seedp, uint32_t salt) {
+  constexpr int D = 64, S = 128, NS = D / 16, NJ = D / 32, IMG = KT * D * 2;
+  constexpr int DS_BYTES = S * S * 2;
+  __shared__ __attribute__((aligned(16))) char smem[6 * IMG + DS_BYTES + 2 * S * 4];
+  char* Qi = smem;               // two 64-row images each, rows at swap23 (as Tile::store)
+  char* Oi = smem + 2 * IMG;
+  char* Ki = smem + 4 * IMG;     // 128 rows in natural order
+  char* dSi = smem + 6 * IMG;    // [query at swap23][key] bf16, 256-B rows
+  float* Ls = reinterpret_cast<float*>(dSi + DS_BYTES);
+  float* Dt = Ls + S;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, hh = lane >> 5, l32 = lane & 31;
+  const int nattn = nseq * H, E = H * D, ld = 3 * E;
+  if ((int)blockIdx.x >= nattn) {   // tail block
+    zero_tail_rows(dqkv, (long)ld * 2, tail_start(vl, nseq), vl.T, blockIdx.x - nattn);
+    return;
+  }
+  const int bh = xcd_remap(blockIdx.x, nattn), b = bh / H, hd = bh - b * H;
+  const Seq sq = seq_of<true>(b, hd, bh, max_len, vl);
+  const int L = sq.len;
+  if (L <= 0) return;   // as in the forward
+  const int nq = (L + 31) >> 5;
+  const bool active = 32 * __builtin_amdgcn_readfirstlane(w) < L;   // this wave owns real rows
+  const bf16* Qg = qkv + (size_t)sq.row0 * ld + hd * D;
+  const bf16* Kg = Qg + E;
+  const bf16* Vg = Qg + 2 * E;
+  const bf16* Og = out + (size_t)sq.row0 * E + hd * D;
+  const bf16* dOg = dout + (size_t)sq.row0 * E + hd * D;
+  const uint32_t seed = seedp ? *seedp : 0u;
+  const int row = 32 * w + l32, rc = min(row, L - 1);   // this lane's key (phase A) and query (0, B)
+  // ---- phase 0
+  {
+    constexpr int CH = D / 8;
+    Tile<D> q0, o0, k0;
+    q0.load(Qg, ld, tid, min(L, KT));
+    o0.load(dOg, E, tid, min(L, KT));
+    k0.load(Kg, ld, tid, min(L, KT));
+    if (L > KT) {   // the second images, fetched behind the first ones' loads
+      Tile<D> q1, o1, k1;
+      q1.load(Qg + (size_t)KT * ld, ld, tid, L - KT);
+      o1.load(dOg + (size_t)KT * E, E, tid, L - KT);
+      k1.load(Kg + (size_t)KT * ld, ld, tid, L - KT);
+      q1.store(Qi + IMG, tid);
+      o1.store(Oi + IMG, tid);
+#pragma unroll
+      for (int j = 0; j < Tile<D>::N; ++j) {
+        const int c = tid + NT * j, r = c / CH, ch = c % CH;
+        *reinterpret_cast<uint4*>(Ki + off<D>(r + KT, ch)) = k1.v[j];
+      }
+    }
+    if (active) {
+      float dt = 0.f;
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        const bf16x8 of = gfrag(dOg, E, rc, s, lane), ov = gfrag(Og, E, rc, s, lane);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dt += (float)of[e] * (float)ov[e];
+      }
+      dt += __shfl_xor(dt, 32, 64);
+      if (hh == 0) {   // queries past the length: lse = +inf makes their probabilities exactly 0
+        Dt[row] = row < L ? dt : 0.f;
+        Ls[row] = row < L ? lse[sq.stat0 + rc] * LOG2E : INFINITY;
+      }
+    }
+    q0.store(Qi, tid);
+    o0.store(Oi, tid);
+#pragma unroll
+    for (int j = 0; j < Tile<D>::N; ++j) {   // K rows in natural order
+      const int c = tid + NT * j, r = c / CH, ch = c % CH;
+      *reinterpret_cast<uint4*>(Ki + off<D>(r, ch)) = k0.v[j];
+    }
+  }
+  // this wave's keys: K / V fragments (B operands); keys past the length get a -inf bias
+  bf16x8 kf[NS], vf[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    kf[s] = gfrag(Kg, ld, rc, s, lane);
+    vf[s] = gfrag(Vg, ld, rc, s, lane);
+  }
+  const float kbl = row < L ? 0.f : -INFINITY;
+  __syncthreads();
+  // ---- phase A
+  if (active) {
+    f32x16 dk[NJ], dv[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      zero(dk[j]);
+      zero(dv[j]);
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const char* Qt = Qi + t * IMG;
+      const char* Ot = Oi + t * IMG;
+      f32x16 sc[2], dp[2];   // C[q][key]: lane = key, register r = query 64t + 32i + acc_row(r, hh)
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+        if (2 * t + i < nq) {
+          zero(sc[i]);
+          zero(dp[i]);
+#pragma unroll
+          for (int s = 0; s < NS; ++s) {
+            sc[i] = mfma(rowf<D>(Qt, 32 * i + l32, s, lane), kf[s], sc[i]);
+            dp[i] = mfma(rowf<D>(Ot, 32 * i + l32, s, lane), vf[s], dp[i]);
+          }
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const int q0 = KT * t + 32 * i + 8 * g + 4 * hh;   // registers 4g..4g+3: queries q0..q0+3
+            const f32x4 L4 = *reinterpret_cast<const f32x4*>(Ls + q0);
+            const f32x4 D4 = *reinterpret_cast<const f32x4*>(Dt + q0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const int r = 4 * g + e;
+              const float p = __builtin_amdgcn_exp2f(sc[i][r] * sl2 + kbl - L4[e]);
+              float d = dp[i][r], pd = p;
+              if constexpr (DROP) {
+                const bool kp = keep(seed, salt, (((uint32_t)bh * max_len + q0 + e) * max_len + row), thr);
+                d = kp ? d * inv_keep : 0.f;
+                pd = kp ? p * inv_keep : 0.f;
+              }
+              const float ds = scale * p * (d - D4[e]);
+              dp[i][r] = ds;
+              sc[i][r] = pd;
+              *reinterpret_cast<bf16*>(dSi + off<128>(swap23(q0 + e), row >> 3) + (row & 7) * 2) = (bf16)ds;
+            }
+          }
+#pragma unroll
+          for (int s = 0; s < 2; ++s) {
+            const bf16x8 pb = acc_frag(sc[i], s);
+            const bf16x8 sb = acc_frag(dp[i], s);
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+              dv[j] = mfma(trf<D>(Ot, 32 * j, 32 * i + 16 * s, lane), pb, dv[j]);
+              dk[j] = mfma(trf<D>(Qt, 32 * j, 32 * i + 16 * s, lane), sb, dk[j]);
+            }
+          }
+        }
+    }
+    if (row < L) {
+      bf16* dst = dqkv + ((size_t)sq.row0 + row) * ld + hd * D;
+      store_rows<NJ>(dst + E, dk, lane);
+      store_rows<NJ>(dst + 2 * E, dv, lane);
+    }
+  }
+  __syncthreads();   // every wave's dS is in the image
+  // ---- phase B: dQ^T[d][q] = sum_key K^T[d][key] dS^T[key][q], lane = query, keys below 32 nq
+  if (active) {
+    f32x16 dq[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) zero(dq[j]);
+#pragma unroll
+    for (int s = 0; s < S / 16; ++s)
+      if (s < 2 * nq) {
+        const bf16x8 sb = rowf<128>(dSi, row, s, lane);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) dq[j] = mfma(trf<D>(Ki, 32 * j, 16 * s, lane), sb, dq[j]);
+      }
+    if (row < L) store_rows<NJ>(dqkv + ((size_t)sq.row0 + row) * ld + hd * D, dq, lane);
+  }
+}
+
 // MLC_ATTN_BWD128=0 routes S = 128, D = 64 back to the streaming kernels (fwd_kernel and the
 // dq / dkv pair)
 int g_bwd128 = -1;
+// MLC_ATTN_VARLEN128=0 routes packed calls with max_len <= 128 back to the streaming kernels
+int g_varlen128 = -1;
 
 bool flash_shape_ok(int B, int S, int H, int D) {
   return B > 0 && H > 0 && S >= 1 && (D == 64 || D == 128);
@@ -965,11 +1274,31 @@ bool varlen_shape_ok(const int* cu, int T, int nseq, int max_len, int H, int D) 
   return cu && T > 0 && nseq > 0 && max_len >= 1 && H > 0 && (D == 64 || D == 128);
 }
 
+// the whole-sequence pair takes the call: non-causal, D = 64, max_len <= 128, knob on
+bool varlen128_route(int max_len, int D, int causal) {
+  if (g_varlen128 < 0) {
+    const char* e = getenv("MLC_ATTN_VARLEN128");
+    g_varlen128 = e ? (atoi(e) != 0) : 1;
+  }
+  return g_varlen128 && max_len >= 1 && max_len <= 128 && D == 64 && !causal;
+}
+
 int flash_fwd_varlen(const bf16* qkv, const int* cu, bf16* out, float* lse, int T, int nseq, int max_len, int H, int D,
                      float scale, float p, const uint32_t* seed, uint32_t salt, int causal, hipStream_t st) {
   if (!varlen_shape_ok(cu, T, nseq, max_len, H, D)) return -1;
   const uint32_t t = p > 0.f ? drop_threshold(p) : 0u;
   const float k = p > 0.f ? 1.f / (1.f - p) : 1.f;
+  if (varlen128_route(max_len, D, causal)) {
+    const dim3 grid(nseq * H + TAILB);   // host integers only: fixed under graph replay
+    const VarLen vl{cu, T};
+    if (t)
+      hipLaunchKernelGGL((fwd128_varlen_kernel<true>), grid, dim3(NT), 0, st, qkv, vl, out, lse, nseq, max_len, H,
+                         scale * LOG2E, t, k, seed, salt);
+    else
+      hipLaunchKernelGGL((fwd128_varlen_kernel<false>), grid, dim3(NT), 0, st, qkv, vl, out, lse, nseq, max_len, H,
+                         scale * LOG2E, t, k, seed, salt);
+    return hipGetLastError();
+  }
   const int nqb = (max_len + 127) / 128;
   const dim3 grid(nseq * H * nqb);   // from nseq_max, H and max_len only: fixed under graph replay
   const AttnBias ab = bias_arg(nullptr, 0, 0, max_len);
@@ -987,6 +1316,17 @@ int flash_bwd_varlen(const bf16* qkv, const int* cu, const bf16* out, const bf16
   if (!varlen_shape_ok(cu, T, nseq, max_len, H, D)) return -1;
   const uint32_t t = p > 0.f ? drop_threshold(p) : 0u;
   const float k = p > 0.f ? 1.f / (1.f - p) : 1.f;
+  if (varlen128_route(max_len, D, causal)) {   // one launch, no dot scratch
+    const dim3 grid(nseq * H + TAILB);
+    const VarLen vl{cu, T};
+    if (t)
+      hipLaunchKernelGGL((bwd128_varlen_kernel<true>), grid, dim3(NT), 0, st, qkv, vl, out, dout, lse, dqkv, nseq,
+                         max_len, H, scale, scale * LOG2E, t, k, seed, salt);
+    else
+      hipLaunchKernelGGL((bwd128_varlen_kernel<false>), grid, dim3(NT), 0, st, qkv, vl, out, dout, lse, dqkv, nseq,
+                         max_len, H, scale, scale * LOG2E, t, k, seed, salt);
+    return hipGetLastError();
+  }
   const int nb = (max_len + 127) / 128;
   const dim3 grid(nseq * H * nb);
   const AttnBias ab = bias_arg(nullptr, 0, 0, max_len);
@@ -1089,6 +1429,12 @@ MLC_EXPORT int mlc_flash_bwd_masked(const bf16* qkv, const float* key_bias, cons
 // zero-filled out / lse / dqkv.  Dropout drops element ((b*H + h)*max_len + q)*max_len + key
 // (q, key within the sequence), what the padded call at S = max_len drops.  causal != 0 as in
 // the masked entry points; no bias operands.
+// Whole-sequence form (mlc_flash_varlen128_ok: not causal, D = 64, max_len <= 128, knob on): one
+// launch per direction, and its tail blocks zero the rows cu[nseq_max] .. T-1 of out / lse
+// (forward) and dqkv (backward), so the caller need not fill them; dot is not touched.  The
+// contract for a cu_seqlens that breaks the rules stays "wrong numbers, never an out-of-bounds
+// access", but rows that no block owns (a gap between slots, say) are then undefined, not zero.
+// lse has one layout in both forms, so a forward by one form serves a backward by the other.
 MLC_EXPORT int mlc_flash_fwd_varlen(const bf16* qkv, const int* cu_seqlens, bf16* out, float* lse, int T,
                                     int nseq_max, int max_len, int H, int D, float scale, float p,
                                     const uint32_t* seed, uint32_t salt, int causal, hipStream_t st) {
@@ -1101,6 +1447,21 @@ MLC_EXPORT int mlc_flash_bwd_varlen(const bf16* qkv, const int* cu_seqlens, cons
                                     int causal, hipStream_t st) {
   return flash_bwd_varlen(qkv, cu_seqlens, out, dout, lse, dot, dqkv, T, nseq_max, max_len, H, D, scale, p, seed,
                           salt, causal, st);
+}
+
+// 1: a packed call of this shape runs the whole-sequence pair (fwd128_varlen / bwd128_varlen)
+MLC_EXPORT int mlc_flash_varlen128_ok(int max_len, int D, int causal) {
+  return varlen128_route(max_len, D, causal) ? 1 : 0;
+}
+
+// A/B knob of the whole-sequence packed pair: key 0 = enable (MLC_ATTN_VARLEN128, default 1);
+// value < 0 only reads.  Returns the previous value.
+MLC_EXPORT int mlc_flash_varlen128_get_set(int key, int value) {
+  if (key != 0) return -1;
+  varlen128_route(0, 0, 0);   // resolves the environment once
+  const int old = g_varlen128;
+  if (value >= 0) g_varlen128 = value ? 1 : 0;
+  return old;
 }
 
 // A/B knob of the S = 128 fused backward: value 0 / 1 sets it, < 0 only reads; returns the

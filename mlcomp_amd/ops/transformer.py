@@ -433,13 +433,22 @@ def _seq_slices(cu_seqlens):
     return [(b, c0, c1) for b, (c0, c1) in enumerate(zip(cu, cu[1:])) if c1 > c0]
 
 
+def _varlen_alloc(max_len, D, causal):
+    """How a packed call's outputs are allocated: the whole-sequence kernels (``max_len`` <= 128,
+    D = 64, not causal, knob ``MLC_ATTN_VARLEN128`` on) zero the rows of no sequence themselves,
+    the streaming kernels write real rows only and want zero-filled buffers."""
+    whole = _lib.load().mlc_flash_varlen128_ok(int(max_len), int(D), int(bool(causal))) == 1
+    return torch.empty if whole else torch.zeros
+
+
 def attn_fwd_varlen(qkv, cu_seqlens, max_len, H, scale, p=0.0, seed=None, salt=0, head_dim: int = 64, *,
                     causal: bool = False, key_bias=None, attn_bias=None):
     """Fused attention over packed sequences: ``qkv`` [T, 3*H*D] holds the sequences back to
     back, sequence b in rows cu_seqlens[b] .. cu_seqlens[b+1]-1 (int32 [nseq_max + 1]; equal
     neighbours = an empty slot), every length <= ``max_len``.  Returns (ctx [T, H*D] bf16, lse
     [H*T] fp32, index h*T + row).  Rows that belong to no sequence (cu[-1] .. T-1) come back as
-    exact zeros (zero-filled outputs; the kernels write real rows only).  Dropout drops element
+    exact zeros (the whole-sequence kernels' tail blocks write them; the streaming kernels get
+    zero-filled outputs and write real rows only).  Dropout drops element
     ((b*H + h)*max_len + q)*max_len + key with q / key relative to the sequence - exactly what
     :func:`attn_fwd` over the same sequences padded to S = max_len drops.  ``causal`` as in
     :func:`attn_fwd`; bias operands are refused (ValueError).  ``cu_seqlens`` is validated
@@ -457,8 +466,9 @@ def attn_fwd_varlen(qkv, cu_seqlens, max_len, H, scale, p=0.0, seed=None, salt=0
     if _cuda(qkv):
         assert attn_supported(max_len, D) and qkv.is_contiguous() and tuple(qkv.shape) == (T, 3 * H * D)
         cu = cu_seqlens.to(device=qkv.device, dtype=torch.int32).contiguous()
-        ctx = torch.zeros(T, H * D, device=qkv.device, dtype=torch.bfloat16)
-        lse = torch.zeros(H * T, device=qkv.device, dtype=torch.float32)
+        new = _varlen_alloc(max_len, D, causal)
+        ctx = new(T, H * D, device=qkv.device, dtype=torch.bfloat16)
+        lse = new(H * T, device=qkv.device, dtype=torch.float32)
         _lib.call('mlc_flash_fwd_varlen', _lib.ptr(qkv), _lib.ptr(cu), _lib.ptr(ctx), _lib.ptr(lse), T, nseq,
                   int(max_len), H, D, float(scale), float(p), _lib.ptr(seed), salt, int(bool(causal)), _lib.stream())
         return ctx, lse
@@ -494,7 +504,7 @@ def attn_bwd_varlen(qkv, cu_seqlens, max_len, dctx, lse, H, scale, p=0.0, seed=N
         assert dctx.is_contiguous() and tuple(dctx.shape) == (T, H * D) and lse.numel() == H * T
         assert ctx is not None and ctx.is_contiguous() and ctx.shape == dctx.shape
         cu = cu_seqlens.to(device=qkv.device, dtype=torch.int32).contiguous()
-        dqkv = torch.zeros_like(qkv)
+        dqkv = _varlen_alloc(max_len, D, causal)(T, 3 * H * D, device=qkv.device, dtype=torch.bfloat16)
         dot = torch.empty(H * T, device=qkv.device, dtype=torch.float32)
         _lib.call('mlc_flash_bwd_varlen', _lib.ptr(qkv), _lib.ptr(cu), _lib.ptr(ctx), _lib.ptr(dctx), _lib.ptr(lse),
                   _lib.ptr(dot), _lib.ptr(dqkv), T, nseq, int(max_len), H, D, float(scale), float(p), _lib.ptr(seed),

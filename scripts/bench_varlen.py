@@ -2,10 +2,13 @@
 
 ``attn``: BERT-base attention (H = 12, D = 64, max_len = 128), lengths drawn once (seeded,
 uniform in [8, 128]) to fill T = 4096: varlen forward + backward against the padded flash
-kernels over the same sequences at [n, 128] with a -inf key bias.
-``step``: the BERT-base training step, ``pack_tokens=4096`` against the padded step at
-32 x 128, on the same seeded variable-length data (each loads its batches the way the runner
-would); sequences/s and real tokens/s.
+kernels over the same sequences at [n, 128] with a -inf key bias.  The packed call is timed in
+both forms through ``mlc_flash_varlen128_get_set``: ``whole`` (the whole-sequence pair) and
+``varlen`` (the streaming kernels and their zero fills).
+``step``: the BERT-base training step, ``pack_tokens=4096`` (``packed``: captured with the
+whole-sequence attention on, ``packed_off``: off) against the padded step at 32 x 128, on the
+same seeded variable-length data (each loads its batches the way the runner would);
+sequences/s and real tokens/s.
 
 Every pair is timed back to back and the pairs are repeated; medians and spreads (max - min)
 are reported.  Usage: ``python scripts/bench_varlen.py attn|step [--pairs N]``."""
@@ -21,7 +24,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from mlcomp_amd.ops import transformer as Tx  # noqa: E402
+from mlcomp_amd.ops import _lib, transformer as Tx  # noqa: E402
 from mlcomp_amd.train.data import TokenBudgetBatchSampler  # noqa: E402
 from mlcomp_amd.train.graphed import work_stream  # noqa: E402
 
@@ -70,24 +73,35 @@ def bench_attn(pairs, iters=50):
     pq, pd = pq.view(n * MAX_LEN, -1), pd.view(n * MAX_LEN, -1)
     seed = torch.tensor([3], dtype=torch.int32, device=DEV)
 
-    def varlen():
+    def packed():
         ctx, lse = Tx.attn_fwd_varlen(qkv, cu, MAX_LEN, H, scale, 0.1, seed, 16, head_dim=D)
         Tx.attn_bwd_varlen(qkv, cu, MAX_LEN, dctx, lse, H, scale, 0.1, seed, 16, head_dim=D, ctx=ctx)
+
+    def whole():          # the whole-sequence pair (knob on)
+        knob(0, 1)
+        packed()
+
+    def varlen():         # the streaming varlen kernels and their zero fills (knob off)
+        knob(0, 0)
+        packed()
 
     def padded():
         ctx, lse = Tx.attn_fwd(pq, kb, n, MAX_LEN, H, scale, 0.1, seed, 16, head_dim=D)
         Tx.attn_bwd(pq, kb, pd, lse, n, MAX_LEN, H, scale, 0.1, seed, 16, head_dim=D, ctx=ctx)
 
-    res = {'varlen': [], 'padded': []}
+    knob = _lib.load().mlc_flash_varlen128_get_set
+    old = knob(0, -1)
+    res = {'whole': [], 'varlen': [], 'padded': []}
     with work_stream(torch.device(DEV)):
-        for fn in (varlen, padded):
+        for fn in (whole, varlen, padded):
             timed(fn, 10)
         for _ in range(pairs):
+            res['whole'].append(timed(whole, iters))
             res['varlen'].append(timed(varlen, iters))
             res['padded'].append(timed(padded, iters))
+    knob(0, old)
     print(json.dumps({'bench': 'attn_fwd_bwd_us', 'H': H, 'D': D, 'max_len': MAX_LEN, 'T': T, 'nseq': n,
-                      'tokens': sum(lengths), 'varlen': summary(res['varlen']), 'padded': summary(res['padded']),
-                      'raw': res}))
+                      'tokens': sum(lengths), **{k: summary(v) for k, v in res.items()}, 'raw': res}))
 
 
 def bench_step(pairs, steps=20):
@@ -106,7 +120,11 @@ def bench_step(pairs, steps=20):
     packed_b = batches(list(TokenBudgetBatchSampler(lens, T, nseq_max)))
     padded_b = batches([list(range(i, i + 32)) for i in range(0, len(lens) - 31, 32)])
     mk = lambda **kw: NativeBertStep('bert-base', device=DEV, use_graph=True, warmup_eager=2, **kw)  # noqa: E731
+    # the packed step twice: its graph is captured with the whole-sequence attention knob on / off
+    knob = _lib.load().mlc_flash_varlen128_get_set
+    old = knob(0, -1)
     packed = mk(batch=nseq_max, seq_len=MAX_LEN, pack_tokens=T)
+    packed_off = mk(batch=nseq_max, seq_len=MAX_LEN, pack_tokens=T)
     padded = mk(batch=32, seq_len=MAX_LEN)
 
     def run(step, data, k0, n):
@@ -123,15 +141,19 @@ def bench_step(pairs, steps=20):
         dt = time.perf_counter() - t0
         return seqs / dt, toks / dt
 
-    for st, data in ((packed, packed_b), (padded, padded_b)):
+    arms = (('packed', packed, packed_b, 1), ('packed_off', packed_off, packed_b, 0),
+            ('padded', padded, padded_b, old))
+    for _, st, data, on in arms:
+        knob(0, on)
         run(st, data, 0, 6)          # eager warm-up, capture, first replays
-    res = {'packed_seq_s': [], 'packed_tok_s': [], 'padded_seq_s': [], 'padded_tok_s': []}
+    knob(0, old)
+    res = {name + unit: [] for name, _, _, _ in arms for unit in ('_seq_s', '_tok_s')}
     for p in range(pairs):
-        for name, st, data in (('packed', packed, packed_b), ('padded', padded, padded_b)):
+        for name, st, data, _ in arms:
             s, t = run(st, data, 6 + p * steps, steps)
             res[name + '_seq_s'].append(s)
             res[name + '_tok_s'].append(t)
-    assert packed.graph is not None and padded.graph is not None
+    assert all(st.graph is not None for _, st, _, _ in arms)
     print(json.dumps({'bench': 'bert_base_step', 'pack_tokens': T, 'nseq_max': nseq_max, 'padded': '32x128',
                       'lengths': 'uniform[8,128]', 'steps_per_run': steps,
                       'mean_seqs_per_packed_step': round(sum(b[0].shape[0] for b in packed_b) / len(packed_b), 1),
