@@ -52,6 +52,12 @@ def _run(cmd):
     return r
 
 
+# extra compile flags of single kernel files.  embed.hip: scalar fp32 only, no packed fp32
+# VALU forms (v_pk_{add,mul,fma}_f32) - a whole-file flag and not flash_attn.hip's per-kernel
+# target attribute, which keeps atomicAdd / __syncthreads from being inlined into the kernel
+FILE_FLAGS = {'embed.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']}
+
+
 def build_kernels(verbose=False, jobs=None):
     os.makedirs(OUT, exist_ok=True)
     bench = sorted(glob.glob(os.path.join(ROOT, 'csrc', 'bench', '*.hip')))
@@ -69,7 +75,8 @@ def build_kernels(verbose=False, jobs=None):
             todo.append((s, o))
     jobs = jobs or min(8, max(1, len(todo)))
     with cf.ThreadPoolExecutor(jobs) as ex:
-        futs = [ex.submit(_run, [HIPCC] + flags + ['-c', s, '-o', o]) for s, o in todo]
+        futs = [ex.submit(_run, [HIPCC] + flags + FILE_FLAGS.get(os.path.basename(s), []) + ['-c', s, '-o', o])
+                for s, o in todo]
         for f in futs:
             f.result()
     bench_objs = [os.path.join(objdir, os.path.basename(s) + '.o') for s in bench]

@@ -49,6 +49,11 @@ GELU_DERIV = os.environ.get('MLC_GELU_DERIV', '1') == '1'
 # them into the gradient arena, instead of a finalize launch after each LayerNorm backward;
 # the LayerNorm slots are marked ready for the bucketer then.
 LN_DEFER = os.environ.get('MLC_LN_DEFER', '1') == '1'
+# MLC_EMBED_NATIVE=1 (default): on the GPU the embedding gather + LayerNorm is one kernel
+# (Tx.embed_ln_fwd, padded and packed, training and predict), and the packed step's embedding
+# backward (Tx.embed_bwd_packed), slot-weighted cross-entropy (Fn.softmax_ce_slots) and [CLS]
+# gradient scatter (Tx.cls_scatter) are kernels too; 0 keeps the torch gathers / index_add_.
+EMBED_NATIVE = os.environ.get('MLC_EMBED_NATIVE', '1') == '1'
 
 
 class _Dense:
@@ -259,9 +264,12 @@ class _BertLayerFn(torch.autograd.Function):
 class _EmbedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ids, tt, anchor, net: 'NativeBert'):
-        e = net.embed(ids, tt)
-        y, s, m, r = Tx.ln_fwd(e, None, net.ln.g.master, net.ln.b.master, net.c.eps, p_out=net.p_hidden,
-                               seed=net.seed, salt_out=1)
+        if EMBED_NATIVE and ids.is_cuda:
+            y, s, m, r = net.embed_ln(ids, tt, net.pos_ids if ids.dim() == 1 else None, net.p_hidden)
+        else:
+            e = net.embed(ids, tt)
+            y, s, m, r = Tx.ln_fwd(e, None, net.ln.g.master, net.ln.b.master, net.c.eps, p_out=net.p_hidden,
+                                   seed=net.seed, salt_out=1)
         ctx.net = net
         ctx.save_for_backward(ids, tt, s, m, r)
         return y
@@ -275,6 +283,13 @@ class _EmbedFn(torch.autograd.Function):
             net.ln_fin.run()
             for ln in net.all_lns():
                 ln.mark()
+        kernel = EMBED_NATIVE and ds.is_cuda and not _lib.DETERMINISTIC and net.tok_type.grad.shape[0] <= 4
+        if net.packed and kernel:
+            # one kernel over the packed rows: word / position atomics, per-type sums in registers
+            Tx.embed_bwd_packed(ds, ids, tt, net.pos_ids, net.word.grad, net.pos.grad, net.tok_type.grad)
+            for sl in (net.word, net.tok_type, net.pos):
+                net.ctx.arena.mark_ready(sl)
+            return None, None, None, None
         if net.packed:
             # packed rows [T]: the position of a row is pos_ids[row], so the position table takes
             # a gather's gradient like the other two (tail rows carry zero gradient)
@@ -354,6 +369,13 @@ class _HeadFn(torch.autograd.Function):
         pooled = torch.tanh(z.float()).to(torch.bfloat16)
         pd = Tx.dropout(pooled, net.p_hidden, net.seed, 2)
         logits = Fn.linear_fwd(pd, net.cls_w.bf16, net.cls_b.master)
+        if EMBED_NATIVE and logits.is_cuda:   # one kernel, one thread per slot
+            dl, loss = Fn.softmax_ce_slots(logits, labels, net.slot_w, net.loss_sum(), net.correct(),
+                                           num_classes=V)
+            ctx.net = net
+            ctx.save_for_backward(cls, pooled, pd, dl)
+            net._logits = logits
+            return loss
         lf = logits[:, :V].float()
         w = net.slot_w
         real = (w > 0).float()
@@ -385,6 +407,9 @@ class _HeadFn(torch.autograd.Function):
         net.pooler.bwd_params(dz, cls)
         dcls = net.pooler.dgrad(dz)
         net.pooler.mark()
+        if net.packed and EMBED_NATIVE and dcls.is_cuda and net.B <= 1024:
+            # one pass writes all of dh: row cu[b] takes dcls[b], every other row zero
+            return Tx.cls_scatter(dcls, net.cu, net.T), None, None, None
         if net.packed:
             # dcls of an empty slot is exactly zero (its dlogits are), so adding it to whichever
             # row that slot gathered changes nothing; real slots own distinct rows
@@ -546,6 +571,13 @@ class NativeBert:
         e = self.word.bf16[ids].float() + pos.float() + self.tok_type.bf16[tt].float()
         return e.to(torch.bfloat16).view(ids.numel(), -1)
 
+    def embed_ln(self, ids, tt, pos_ids, p_out):
+        """The embedding sum and its LayerNorm (+ output dropout) as one kernel:
+        (y, e, mean, rstd), what ``Tx.ln_fwd`` returns over :meth:`embed`."""
+        return Tx.embed_ln_fwd(ids, tt, pos_ids, self.word.bf16, self.pos.bf16, self.tok_type.bf16,
+                               self.ln.g.master, self.ln.b.master, self.c.eps, p_out=p_out, seed=self.seed,
+                               salt_out=1)
+
     def cls_rows(self, cu=None):
         """Packed mode: the row of every slot's first token, cu[b]; an empty slot (whose cu[b]
         may equal T) gathers the last row instead - any valid row does, its weight is 0."""
@@ -572,10 +604,13 @@ class NativeBert:
         self.train(False)
         try:
             with torch.no_grad():
-                e = (self.word.bf16[ids].float() + self.pos.bf16[:S][None].float()
-                     + self.tok_type.bf16[tt].float()).to(torch.bfloat16).view(B * S, -1)
-                h = Tx.ln_fwd(e, None, self.ln.g.master, self.ln.b.master, self.c.eps, p_out=0.0,
-                              seed=self.seed, salt_out=1)[0]
+                if EMBED_NATIVE and ids.is_cuda:
+                    h = self.embed_ln(ids, tt, None, 0.0)[0]
+                else:
+                    e = (self.word.bf16[ids].float() + self.pos.bf16[:S][None].float()
+                         + self.tok_type.bf16[tt].float()).to(torch.bfloat16).view(B * S, -1)
+                    h = Tx.ln_fwd(e, None, self.ln.g.master, self.ln.b.master, self.c.eps, p_out=0.0,
+                                  seed=self.seed, salt_out=1)[0]
                 for layer in self.layers:
                     h, _ = layer.fwd(h, key_bias)
                 cls = h.view(B, S, -1)[:, 0].contiguous()
@@ -596,8 +631,11 @@ class NativeBert:
         self.train(False)
         try:
             with torch.no_grad():
-                h = Tx.ln_fwd(self.embed(ids, tt, pos_ids), None, self.ln.g.master, self.ln.b.master, self.c.eps,
-                              p_out=0.0, seed=self.seed, salt_out=1)[0]
+                if EMBED_NATIVE and ids.is_cuda:
+                    h = self.embed_ln(ids, tt, pos_ids, 0.0)[0]
+                else:
+                    h = Tx.ln_fwd(self.embed(ids, tt, pos_ids), None, self.ln.g.master, self.ln.b.master,
+                                  self.c.eps, p_out=0.0, seed=self.seed, salt_out=1)[0]
                 for layer in self.layers:
                     h, _ = layer.fwd(h, None)
                 z, _ = self.pooler.fwd(h[self.cls_rows()])

@@ -59,6 +59,11 @@ _SIGS = {
     'mlc_ln_bwd': [vp] * 10 + [i32, i32, f32, f32, vp, u32, u32, vp],
     'mlc_ln_finalize_many': [vp, i32, i32, vp],
     'mlc_embed_bwd': [vp] * 7 + [i32] * 4 + [vp],
+    # embedding + LayerNorm forward, packed embedding backward, packed head (embed.hip)
+    'mlc_embed_ln_fwd': [vp] * 12 + [i32] * 6 + [f32, f32, vp, u32, vp],
+    'mlc_embed_bwd_packed': [vp] * 8 + [i32] * 5 + [vp],
+    'mlc_softmax_ce_slots': [vp] * 7 + [i32] * 4 + [vp],
+    'mlc_cls_scatter': [vp] * 3 + [i32] * 3 + [vp],
     'mlc_softmax_fwd': [vp] * 4 + [i64, i32, i32, f32, f32, vp, u32, vp],
     'mlc_softmax_bwd': [vp] * 3 + [i64, i32, f32, f32, vp, u32, vp],
     'mlc_linear_wgrad_bias': [vp] * 4 + [i32] * 7 + [vp, i64, vp],

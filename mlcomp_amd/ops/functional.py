@@ -1125,6 +1125,35 @@ def softmax_ce(logits, labels, loss_sum, correct=None, scale=None, smoothing=0.0
     return g.to(torch.bfloat16)
 
 
+def softmax_ce_slots(logits, labels, w, loss_sum, correct=None, num_classes=None):
+    """Slot-weighted softmax cross-entropy of the packed BERT head over the first
+    ``num_classes`` columns of ``logits`` ([n, ld] fp32): slot b counts with weight ``w[b]``
+    (1/nseq for a real slot, 0 for an empty one).  Accumulates the summed loss (and #correct)
+    of the slots with w > 0 into fp32 scalars; returns (dl, wloss): bf16 dlogits [n, ld] =
+    (softmax - target) * w, zero in the padding columns, and the 0-dim fp32 sum of nll * w."""
+    n, ld = logits.shape
+    V = num_classes or ld
+    if _cuda(logits):
+        dl = torch.empty(n, ld, device=logits.device, dtype=torch.bfloat16)
+        wloss = torch.empty(1, device=logits.device, dtype=torch.float32)
+        logits, labels, w = logits.float().contiguous(), labels.contiguous(), w.contiguous()
+        _lib.call('mlc_softmax_ce_slots', _lib.ptr(logits), _lib.ptr(labels), _lib.ptr(w), _lib.ptr(dl),
+                  _lib.ptr(loss_sum), _lib.ptr(correct), _lib.ptr(wloss), n, V, ld, V, _lib.stream())
+        return dl, wloss.view(())
+    lf = logits[:, :V].float()
+    real = (w > 0).float()
+    logp = torch.log_softmax(lf, 1)
+    nll = -logp.gather(1, labels[:, None])[:, 0]
+    loss_sum.add_((nll * real).sum())
+    if correct is not None:
+        correct.add_(((lf.argmax(1) == labels).float() * real).sum())
+    g = torch.exp(logp)
+    g.scatter_add_(1, labels[:, None], torch.full_like(nll, -1.0)[:, None])
+    dl = torch.zeros_like(logits, dtype=torch.bfloat16)
+    dl[:, :V] = (g * w[:, None]).to(torch.bfloat16)  # an empty slot: exactly zero
+    return dl, (nll * w).sum()
+
+
 # ---------------------------------------------------------------- layout helpers
 def nchw_to_nhwc(x, pad_to=None):
     N, C, H, W = x.shape

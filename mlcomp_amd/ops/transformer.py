@@ -141,6 +141,80 @@ def embed_bwd(ds, ids, tt, word_grad, pos_grad, tok_grad):
     pos_grad[:S].add_(d.view(B, S, H).sum(0))
 
 
+def embed_ln_fwd(ids, tt, pos_ids, word, pos, tok, gamma, beta, eps=1e-12, p_out=0.0, seed=None, salt_out=0):
+    """e = bf16((word[ids] + pos[p]) + tok[tt]) and y = dropout_out(LN(e)) in one kernel
+    (``mlc_embed_ln_fwd``); returns (y, e, mean, rstd) as ``ln_fwd`` over the gathered sum does.
+    ``ids`` / ``tt`` int64 [B, S] with ``pos_ids`` None (the position of a token is its column),
+    or packed [T] with the position of every row in ``pos_ids``; ``tt`` None: type 0.  Tables
+    bf16 [rows, H].  The kernel clamps every index into its table; the CPU path indexes as torch
+    does."""
+    T, H = ids.numel(), word.shape[1]
+    if pos_ids is None:
+        assert ids.dim() == 2, 'without pos_ids the position of a token is its column: ids [B, S]'
+    S = ids.shape[-1]
+    if _cuda(word):
+        e = torch.empty(T, H, device=word.device, dtype=torch.bfloat16)
+        y = torch.empty_like(e)
+        mean = torch.empty(T, device=word.device, dtype=torch.float32)
+        rstd = torch.empty(T, device=word.device, dtype=torch.float32)
+        # contiguous copies bound to names (see embed_bwd)
+        idc = ids.contiguous()
+        ttc = tt.contiguous() if tt is not None else None
+        pc = pos_ids.contiguous() if pos_ids is not None else None
+        _lib.call('mlc_embed_ln_fwd', _lib.ptr(idc), _lib.ptr(ttc), _lib.ptr(pc), _lib.ptr(word), _lib.ptr(pos),
+                  _lib.ptr(tok), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(e), _lib.ptr(y), _lib.ptr(mean),
+                  _lib.ptr(rstd), T, S, H, word.shape[0], pos.shape[0], tok.shape[0], float(eps), float(p_out),
+                  _lib.ptr(seed), salt_out, _lib.stream())
+        return y, e, mean, rstd
+    p = pos[pos_ids] if pos_ids is not None else pos[:S][None]
+    t = tok[tt] if tt is not None else tok[0]
+    e = (word[ids].float() + p.float() + t.float()).to(torch.bfloat16).view(T, H)
+    return ln_fwd(e, None, gamma, beta, eps, p_out=p_out, seed=seed, salt_out=salt_out)
+
+
+_EMB_PACKED_SCRATCH = {}
+
+
+def embed_bwd_packed(ds, ids, tt, pos_ids, word_grad, pos_grad, tok_grad):
+    """Embedding gradients of packed rows, ds [T, H] bf16: word_grad[ids] += ds,
+    pos_grad[pos_ids] += ds, tok_grad[tt] += ds (all fp32, accumulated; ids / tt / pos_ids
+    int64 [T]).  One kernel plus a small finish (``mlc_embed_bwd_packed``); at most 4 token types."""
+    T, H = ds.shape
+    if _cuda(ds):
+        ntypes = tok_grad.shape[0]
+        from .functional import workspace_key, workspace_store
+        key = (workspace_key(ds.device), 32 * ntypes * H)
+        store = workspace_store(_EMB_PACKED_SCRATCH)
+        scratch = store.get(key)
+        if scratch is None:    # [32][ntypes][H] per-type partial sums, left zeroed by the kernel
+            scratch = store[key] = torch.zeros(32 * ntypes * H, device=ds.device, dtype=torch.float32)
+        dsc, idc, ttc, pc = ds.contiguous(), ids.contiguous(), tt.contiguous(), pos_ids.contiguous()
+        _lib.call('mlc_embed_bwd_packed', _lib.ptr(dsc), _lib.ptr(idc), _lib.ptr(ttc), _lib.ptr(pc),
+                  _lib.ptr(word_grad), _lib.ptr(pos_grad), _lib.ptr(tok_grad), _lib.ptr(scratch), T, H,
+                  word_grad.shape[0], pos_grad.shape[0], ntypes, _lib.stream())
+        return
+    d = ds.float()
+    word_grad.index_add_(0, ids, d)
+    tok_grad.index_add_(0, tt, d)
+    pos_grad.index_add_(0, pos_ids, d)
+
+
+def cls_scatter(dcls, cu, T: int):
+    """The packed [CLS] gather's gradient: dh [T, H] bf16, row min(cu[b], T-1) takes dcls[b]
+    (slots that share a row are summed in fp32 and rounded once), every other row is zero.
+    ``dcls`` [n, H] bf16, ``cu`` int32 [n + 1]; one pass that writes all of dh
+    (``mlc_cls_scatter``, n <= 1024)."""
+    n, H = dcls.shape
+    if _cuda(dcls):
+        dh = torch.empty(T, H, device=dcls.device, dtype=torch.bfloat16)
+        dc, cc = dcls.contiguous(), cu.contiguous()
+        _lib.call('mlc_cls_scatter', _lib.ptr(dc), _lib.ptr(cc), _lib.ptr(dh), n, T, H, _lib.stream())
+        return dh
+    dh = torch.zeros(T, H, device=dcls.device, dtype=torch.float32)
+    dh.index_add_(0, cu[:-1].long().clamp(max=T - 1), dcls.float())
+    return dh.to(torch.bfloat16)
+
+
 class LnFinalizer:
     """Finalizes the dgamma / dbeta of many LayerNorms in ONE launch
     (``mlc_ln_finalize_many``): each entry's ``ln_bwd(..., defer_finalize=True)`` left its
@@ -663,5 +737,5 @@ def dropout(x, p, seed, salt):
     return torch.where(m, x.float() / (1 - p), torch.zeros_like(x, dtype=torch.float32)).to(x.dtype)
 
 
-__all__ = ['ln_fwd', 'ln_bwd', 'LnFinalizer', 'embed_bwd', 'softmax_fwd', 'softmax_bwd', 'dense_fwd', 'dense_dgrad', 'dact_gelu', 'colsum_acc',
+__all__ = ['ln_fwd', 'ln_bwd', 'LnFinalizer', 'embed_bwd', 'embed_ln_fwd', 'embed_bwd_packed', 'cls_scatter', 'softmax_fwd', 'softmax_bwd', 'dense_fwd', 'dense_dgrad', 'dact_gelu', 'colsum_acc',
            'dropout', 'keep_mask', 'attn_fwd_varlen', 'attn_bwd_varlen', 'check_cu_seqlens']
