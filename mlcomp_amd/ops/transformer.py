@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import math
 import os
+import struct
 from typing import Optional, Tuple
 
 import torch
@@ -27,14 +28,22 @@ def _hash(seed: int, salt: int, idx: torch.Tensor) -> torch.Tensor:
     return x
 
 
+def drop_threshold(p: float) -> int:
+    """``drop_threshold`` of csrc/kernels/dropout.h: ``(uint32_t)(p * 16777216.0f)`` with p
+    already rounded to fp32 (a power-of-two scaling, exact in fp32).  ``int(p * 2**24)`` on
+    the double p is one lower for p = 0.3, 0.6 and 0.8, and the element whose hash lands
+    there would be kept here and dropped by every kernel."""
+    (p32,) = struct.unpack('f', struct.pack('f', p))
+    return int(p32 * 16777216.0)
+
+
 def keep_mask(shape, p: float, seed: int, salt: int, device=None) -> torch.Tensor:
     """Same keep decisions as the kernels for a contiguous tensor of ``shape``."""
     n = 1
     for s in shape:
         n *= s
     idx = torch.arange(n, dtype=torch.int64, device=device)
-    thr = int(p * 16777216.0)
-    return ((_hash(seed, salt, idx) >> 8) >= thr).reshape(shape)
+    return ((_hash(seed, salt, idx) >> 8) >= drop_threshold(p)).reshape(shape)
 
 
 def _seed_val(seed) -> int:
@@ -499,7 +508,7 @@ def _seq_keep(b, H, L, max_len, p, seed, salt):
     q = torch.arange(L, dtype=torch.int64)[None, :, None]
     k = torch.arange(L, dtype=torch.int64)[None, None, :]
     idx = ((b * H + h) * max_len + q) * max_len + k
-    return (_hash(_seed_val(seed), salt, idx) >> 8) >= int(p * 16777216.0)
+    return (_hash(_seed_val(seed), salt, idx) >> 8) >= drop_threshold(p)
 
 
 def _seq_slices(cu_seqlens):
