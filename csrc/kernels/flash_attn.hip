@@ -31,6 +31,12 @@
 // returns before any barrier or LDS traffic, and no key / query tile past the length is
 // fetched.  Dropout keeps the padded layout's element index at S = max_len.
 //
+// Grouped-query attention (the *_gqa entry points; mode bit M_GQA of fwd_kernel / dq_kernel and
+// dkv_gqa_kernel): Hkv <= H key/value heads, qkv rows of (H + 2*Hkv)*D, query head h reads K/V
+// head h / (H / Hkv).  Forward and dQ only change their column geometry; dK / dV is one block
+// per (b, K/V head, 128 keys) that streams the tiles of all its group's query heads and sums
+// their contributions in the fp32 accumulators (no atomics, one store).
+//
 // Work split (one 256-thread block = 4 waves x 32 rows, blocks XCD-remapped so the blocks
 // sharing one (b, h) K/V slice sit on one XCD's L2):
 // * forward: a wave owns 32 queries; scores are computed transposed, S^T = K Q^T
@@ -148,6 +154,7 @@ struct Tile {
 constexpr int M_CAUSAL = 1;   // top-left aligned: query q sees keys <= q
 constexpr int M_BIAS = 2;     // additive fp32 bias[b * sb + h * sh + q * S + key], finite or -inf
 constexpr int M_VARLEN = 4;   // packed sequences: rows and length of slot b from cu_seqlens (no bias operands)
+constexpr int M_GQA = 8;      // grouped-query layout: Hkv K/V heads, qkv rows of (H + 2*Hkv)*D (never with M_VARLEN)
 struct AttnBias {
   const float* p;
   long sb, sh;   // batch / head strides in elements (0 broadcasts)
@@ -176,7 +183,7 @@ __device__ __forceinline__ void load_bias_keys(f32x4 (&bv)[2][4], const float* r
 // dropout index's sequence length) and lse / dot are [H][T].
 struct VarLen {
   const int* cu;   // int32 [nseq_max + 1], device memory
-  int T;
+  int T;           // rows of the packed buffers; in mode M_GQA (never packed) the K/V head count Hkv
 };
 // rows of one (sequence, head): first row, length, and base of its lse / dot entries
 struct Seq {
@@ -229,6 +236,11 @@ __device__ __forceinline__ Geo geo_heavy_first(int H, int nblk, bool last_is_hea
   return g;
 }
 
+// Grouped-query layout (mode bit M_GQA): qkv rows are [Q: H heads | K: Hkv heads | V: Hkv heads],
+// query head h reads K/V head h / (H / Hkv).  Everything else indexed by head (out, lse, dot,
+// the bias, the dropout element) keeps the query head.  Hkv reaches fwd_kernel / dq_kernel in
+// vl.T (the mode is never packed), so the other modes' kernels keep their arguments and code.
+
 // ------------------------------------------------------------------ forward
 template <int D, bool DROP, int MASK>
 __global__ void __launch_bounds__(NT)
@@ -237,16 +249,19 @@ fwd_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, bf1
            const uint32_t* __restrict__ seedp, uint32_t salt, AttnBias ab, VarLen vl) {
   constexpr int NS = D / 16, NJ = D / 32, IMG = KT * D * 2, BUF = 2 * IMG + KT * 4;
   constexpr bool CAUSAL = (MASK & M_CAUSAL) != 0, BIAS = (MASK & M_BIAS) != 0, VARLEN = (MASK & M_VARLEN) != 0;
+  constexpr bool GQA = (MASK & M_GQA) != 0;
+  static_assert(!(GQA && VARLEN), "no packed grouped-query form");
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];   // [buffer][K | V | key bias * log2e]
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, hh = lane >> 5, l32 = lane & 31;
   const Geo G = CAUSAL ? geo_heavy_first(H, nqb, true) : geo(H, nqb);
-  const int E = H * D, ld = 3 * E;
+  const int Hkv = vl.T;   // read in mode M_GQA only
+  const int E = H * D, ld = GQA ? (H + 2 * Hkv) * D : 3 * E;
   const Seq sq = seq_of<VARLEN>(G.b, G.hd, G.bh, S, vl);
   const int L = sq.len;   // this sequence's length (S itself unless packed)
   if (VARLEN && G.blk * 128 >= L) return;   // a grid slot past the sequence (or an empty slot): block-uniform
   const bf16* Qg = qkv + (size_t)sq.row0 * ld + G.hd * D;
-  const bf16* Kg = Qg + E;
-  const bf16* Vg = Qg + 2 * E;
+  const bf16* Kg = GQA ? Qg + (H - G.hd + G.hd / (H / Hkv)) * D : Qg + E;
+  const bf16* Vg = GQA ? Kg + Hkv * D : Qg + 2 * E;
   const int q = G.blk * 128 + 32 * w + l32;
   const int qc = min(q, L - 1);
   bf16x8 qf[NS];
@@ -374,16 +389,19 @@ dq_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, cons
           const uint32_t* __restrict__ seedp, uint32_t salt, AttnBias ab, VarLen vl) {
   constexpr int NS = D / 16, NJ = D / 32, IMG = KT * D * 2, BUF = 2 * IMG + KT * 4;
   constexpr bool CAUSAL = (MASK & M_CAUSAL) != 0, BIAS = (MASK & M_BIAS) != 0, VARLEN = (MASK & M_VARLEN) != 0;
+  constexpr bool GQA = (MASK & M_GQA) != 0;
+  static_assert(!(GQA && VARLEN), "no packed grouped-query form");
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];   // [buffer][K | V | key bias * log2e]
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, hh = lane >> 5, l32 = lane & 31;
   const Geo G = CAUSAL ? geo_heavy_first(H, nqb, true) : geo(H, nqb);
-  const int E = H * D, ld = 3 * E;
+  const int Hkv = vl.T;   // read in mode M_GQA only
+  const int E = H * D, ld = GQA ? (H + 2 * Hkv) * D : 3 * E;
   const Seq sq = seq_of<VARLEN>(G.b, G.hd, G.bh, S, vl);
   const int L = sq.len;
   if (VARLEN && G.blk * 128 >= L) return;   // as in fwd_kernel
   const bf16* Qg = qkv + (size_t)sq.row0 * ld + G.hd * D;
-  const bf16* Kg = Qg + E;
-  const bf16* Vg = Qg + 2 * E;
+  const bf16* Kg = GQA ? Qg + (H - G.hd + G.hd / (H / Hkv)) * D : Qg + E;
+  const bf16* Vg = GQA ? Kg + Hkv * D : Qg + 2 * E;
   const bf16* Og = out + (size_t)sq.row0 * E + G.hd * D;
   const bf16* dOg = dout + (size_t)sq.row0 * E + G.hd * D;
   const int q = G.blk * 128 + 32 * w + l32;
@@ -613,6 +631,160 @@ dkv_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, con
     bf16* dst = dqkv + ((size_t)sq.row0 + key) * ld + G.hd * D;
     store_rows<NJ>(dst + E, dk, lane);
     store_rows<NJ>(dst + 2 * E, dv, lane);
+  }
+}
+
+// ------------------------------------------------------------------ backward: dK, dV, grouped-query
+// One K/V head j receives gradient from the G = H / Hkv query heads j*G .. j*G + G-1.  Block
+// (b, j, blk) owns 128 keys of K/V head j (wave w 32 of them, lane = key, as in dkv_kernel),
+// loads their K / V fragments once and keeps dK^T / dV^T in registers across the whole group:
+// the sum over the group is fp32 in the MFMA accumulators with one rounding to bf16 at the
+// single store - no atomics, no G-times-larger scratch, nothing a deterministic mode changes.
+// The Q / dO / lse / dot tiles of all G heads form ONE stream of G * ntl steps, step i being
+// (g, t) = (i / ntl, t0 + i % ntl); the prefetch of step i + 1 is issued while step i computes,
+// across a head boundary too, so the pipeline is primed once per block.  The staging buffer
+// alternates on i: with ntl odd, tiles (g, nt-1) and (g+1, t0) have the same tile parity, and
+// alternating on t (dkv_kernel's rule) would overwrite the image being read.
+// What depends on the head follows g (the tiles' column, lse / dot rows, the bias column
+// pointer, the dropout element's b*H + h); the causal tests depend on t alone.  With G = 1 the
+// loop is dkv_kernel's, step for step.
+template <int D, bool DROP, int MASK>
+__global__ void __launch_bounds__(NT)
+dkv_gqa_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, const bf16* __restrict__ dout,
+               const float* __restrict__ lse, const float* __restrict__ dot, bf16* __restrict__ dqkv, int S, int H,
+               int Hkv, int nkb, float scale, float sl2, uint32_t thr, float inv_keep,
+               const uint32_t* __restrict__ seedp, uint32_t salt, AttnBias ab) {
+  constexpr int NS = D / 16, NJ = D / 32, IMG = KT * D * 2, BUF = 2 * IMG + 2 * KT * 4;
+  constexpr bool CAUSAL = (MASK & M_CAUSAL) != 0, BIAS = (MASK & M_BIAS) != 0;
+  // [buffer][Q image | dO image | lse*log2e [64] | dot [64]]
+  __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, hh = lane >> 5, l32 = lane & 31;
+  // G.hd is the K/V head j, G.bh = b*Hkv + j; causal grids heaviest first over B * Hkv
+  const Geo G = CAUSAL ? geo_heavy_first(Hkv, nkb, false) : geo(Hkv, nkb);
+  const int NG = H / Hkv, E = H * D, ld = (H + 2 * Hkv) * D;
+  const int h0 = G.hd * NG;   // the group's first query head
+  const bf16* Qg = qkv + (size_t)G.b * S * ld + h0 * D;
+  const bf16* Kg = qkv + (size_t)G.b * S * ld + (H + G.hd) * D;
+  const bf16* Vg = Kg + Hkv * D;
+  const bf16* dOg = dout + (size_t)G.b * S * E + h0 * D;
+  const size_t stat0 = ((size_t)G.b * H + h0) * S;   // lse / dot of (b, h0); head g is g*S further on
+  const int key = G.blk * 128 + 32 * w + l32;
+  const int kc = min(key, S - 1);
+  bf16x8 kf[NS], vf[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    kf[s] = gfrag(Kg, ld, kc, s, lane);
+    vf[s] = gfrag(Vg, ld, kc, s, lane);
+  }
+  const float kbl = key_bias ? key_bias[(size_t)G.b * S + kc] * LOG2E : 0.f;
+  const uint32_t seed = seedp ? *seedp : 0u;
+  f32x16 dk[NJ], dv[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    zero(dk[j]);
+    zero(dv[j]);
+  }
+  Tile<D> tq, to;
+  float ld_v = 0.f;   // this thread's lse / dot element of the next step (threads 0..127)
+  auto fetch = [&](int g, int t) {
+    const int valid = min(KT, S - t * KT);
+    tq.load(Qg + g * D + (size_t)t * KT * ld, ld, tid, valid);
+    to.load(dOg + g * D + (size_t)t * KT * E, E, tid, valid);
+    // queries past S: lse = +inf makes their probabilities exactly 0
+    const size_t st = stat0 + (size_t)g * S + t * KT;
+    if (tid < KT) ld_v = tid < valid ? lse[st + tid] * LOG2E : INFINITY;
+    else if (tid < 2 * KT) ld_v = tid - KT < valid ? dot[st + tid - KT] : 0.f;
+  };
+  auto put = [&](int i) {
+    char* bp = smem + (i & 1) * BUF;
+    tq.store(bp, tid);
+    to.store(bp + IMG, tid);
+    if (tid < 2 * KT) reinterpret_cast<float*>(bp + 2 * IMG)[tid] = ld_v;
+  };
+  // causal: the first query tile that sees this key block (128 * blk < S, so t0 < nt)
+  const int t0 = CAUSAL ? 2 * G.blk : 0;
+  const int nt = (S + KT - 1) / KT;   // a partial last tile is masked
+  const int nstep = NG * (nt - t0);
+  fetch(0, t0);
+  put(0);
+  __syncthreads();
+  const int wk_first = G.blk * 128 + 32 * __builtin_amdgcn_readfirstlane(w);   // this wave's first key
+  int g = 0, t = t0;
+  for (int i = 0; i < nstep; ++i) {
+    const char* bp = smem + (i & 1) * BUF;
+    const char* Qi = bp;
+    const char* Oi = bp + IMG;
+    const float* Ls = reinterpret_cast<const float*>(bp + 2 * IMG);
+    const float* Ds = Ls + KT;
+    const bool wrap = t + 1 == nt;   // the next step starts the next head (block-uniform)
+    const int gn = wrap ? g + 1 : g, tn = wrap ? t0 : t + 1;
+    if (i + 1 < nstep) fetch(gn, tn);
+    // causal: a wave whose 32 keys all follow the tile's queries has nothing but exact zeros
+    // to add; it still stages and synchronises
+    if (!(CAUSAL && t * KT + KT - 1 < wk_first)) {
+    const bool diag = CAUSAL && t < t0 + 2;   // the tile crosses the diagonal (block-uniform)
+    const int hd = h0 + g;                    // the query head of this step
+    const float* bcol = BIAS ? ab.p + G.b * ab.sb + hd * ab.sh + kc : nullptr;
+    const uint32_t bhq = (uint32_t)(G.b * H + hd) * S;
+    f32x16 sc[2], dp[2];   // C[q][key]: lane = key, register r = query 32i + acc_row(r, hh)
+#pragma unroll
+    for (int i2 = 0; i2 < 2; ++i2) {
+      zero(sc[i2]);
+      zero(dp[i2]);
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        sc[i2] = mfma(rowf<D>(Qi, 32 * i2 + l32, s, lane), kf[s], sc[i2]);
+        dp[i2] = mfma(rowf<D>(Oi, 32 * i2 + l32, s, lane), vf[s], dp[i2]);
+      }
+    }
+#pragma unroll
+    for (int i2 = 0; i2 < 2; ++i2)
+#pragma unroll
+      for (int q4 = 0; q4 < 4; ++q4) {
+        const int q0 = 32 * i2 + 8 * q4 + 4 * hh;   // registers 4*q4..4*q4+3 are queries q0..q0+3
+        const f32x4 L4 = *reinterpret_cast<const f32x4*>(Ls + q0);
+        const f32x4 D4 = *reinterpret_cast<const f32x4*>(Ds + q0);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int r = 4 * q4 + e;
+          float x = sc[i2][r] * sl2 + kbl;
+          // padded queries of a tail tile re-read the last row (their lse = +inf zeroes them)
+          if constexpr (BIAS) x += bcol[(size_t)min(t * KT + q0 + e, S - 1) * S] * LOG2E;
+          if constexpr (CAUSAL)
+            if (diag && t * KT + q0 + e < key) x = -INFINITY;   // p exactly 0
+          const float p = __builtin_amdgcn_exp2f(x - L4[e]);
+          float d = dp[i2][r], pd = p;
+          if constexpr (DROP) {
+            const bool kp = keep(seed, salt, (bhq + t * KT + q0 + e) * S + kc, thr);
+            d = kp ? d * inv_keep : 0.f;
+            pd = kp ? p * inv_keep : 0.f;
+          }
+          dp[i2][r] = scale * p * (d - D4[e]);   // dS
+          sc[i2][r] = pd;                        // Pd
+        }
+      }
+#pragma unroll
+    for (int i2 = 0; i2 < 2; ++i2)
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const bf16x8 pb = acc_frag(sc[i2], s);
+        const bf16x8 sb = acc_frag(dp[i2], s);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          dv[j] = mfma(trf<D>(Oi, 32 * j, 32 * i2 + 16 * s, lane), pb, dv[j]);
+          dk[j] = mfma(trf<D>(Qi, 32 * j, 32 * i2 + 16 * s, lane), sb, dk[j]);
+        }
+      }
+    }
+    if (i + 1 < nstep) put(i + 1);
+    __syncthreads();
+    g = gn;
+    t = tn;
+  }
+  if (key < S) {
+    bf16* dst = dqkv + ((size_t)G.b * S + key) * ld;
+    store_rows<NJ>(dst + (H + G.hd) * D, dk, lane);
+    store_rows<NJ>(dst + (H + Hkv + G.hd) * D, dv, lane);
   }
 }
 
@@ -1378,6 +1550,54 @@ int flash_bwd(const bf16* qkv, const float* key_bias, const bf16* out, const bf1
 #undef BWD
   return hipGetLastError();
 }
+
+// Grouped-query calls: always the streaming kernels.  Forward and dQ are the (b, query head,
+// 128-query block) kernels with the M_GQA geometry; dK / dV is one block per (b, K/V head,
+// 128-key block) that sums its group in registers.
+bool gqa_heads_ok(int H, int Hkv) { return Hkv >= 1 && Hkv <= H && H % Hkv == 0; }
+
+int flash_fwd_gqa(const bf16* qkv, const float* key_bias, bf16* out, float* lse, int B, int S, int H, int Hkv, int D,
+                  float scale, float p, const uint32_t* seed, uint32_t salt, int causal, const float* attn_bias,
+                  long stride_b, long stride_h, hipStream_t st) {
+  if (!qkv || !out || !lse || !flash_shape_ok(B, S, H, D) || !gqa_heads_ok(H, Hkv)) return -1;
+  const uint32_t t = p > 0.f ? drop_threshold(p) : 0u;
+  const float k = p > 0.f ? 1.f / (1.f - p) : 1.f;
+  const int mode = mask_mode(causal, attn_bias);
+  const int nqb = (S + 127) / 128;
+  const dim3 grid(B * H * nqb);
+  const AttnBias ab = bias_arg(attn_bias, stride_b, stride_h, S);
+  const VarLen vl{nullptr, Hkv};   // M_GQA: T carries Hkv
+#define FWD(DD, DR, MM) hipLaunchKernelGGL((fwd_kernel<DD, DR, MM | M_GQA>), grid, dim3(NT), 0, st, qkv, key_bias, out, \
+                                           lse, S, H, nqb, scale * LOG2E, t, k, seed, salt, ab, vl)
+  FLASH_DISPATCH(FWD);
+#undef FWD
+  return hipGetLastError();
+}
+
+int flash_bwd_gqa(const bf16* qkv, const float* key_bias, const bf16* out, const bf16* dout, const float* lse,
+                  float* dot, bf16* dqkv, int B, int S, int H, int Hkv, int D, float scale, float p,
+                  const uint32_t* seed, uint32_t salt, int causal, const float* attn_bias, long stride_b,
+                  long stride_h, hipStream_t st) {
+  if (!qkv || !out || !dout || !lse || !dot || !dqkv || !flash_shape_ok(B, S, H, D) || !gqa_heads_ok(H, Hkv))
+    return -1;
+  const uint32_t t = p > 0.f ? drop_threshold(p) : 0u;
+  const float k = p > 0.f ? 1.f / (1.f - p) : 1.f;
+  const int mode = mask_mode(causal, attn_bias);
+  const int nb = (S + 127) / 128;
+  const dim3 grid(B * H * nb), grid_kv(B * Hkv * nb);
+  const AttnBias ab = bias_arg(attn_bias, stride_b, stride_h, S);
+  const VarLen vl{nullptr, Hkv};   // M_GQA: T carries Hkv
+#define BWD(DD, DR, MM)                                                                                               \
+  do {                                                                                                                \
+    hipLaunchKernelGGL((dq_kernel<DD, DR, MM | M_GQA>), grid, dim3(NT), 0, st, qkv, key_bias, out, dout, lse, dot,    \
+                       dqkv, S, H, nb, scale, scale * LOG2E, t, k, seed, salt, ab, vl);                          \
+    hipLaunchKernelGGL((dkv_gqa_kernel<DD, DR, MM>), grid_kv, dim3(NT), 0, st, qkv, key_bias, dout, lse, dot, dqkv,   \
+                       S, H, Hkv, nb, scale, scale * LOG2E, t, k, seed, salt, ab);                                    \
+  } while (0)
+  FLASH_DISPATCH(BWD);
+#undef BWD
+  return hipGetLastError();
+}
 #undef FLASH_MASKS
 #undef FLASH_DISPATCH
 
@@ -1418,6 +1638,28 @@ MLC_EXPORT int mlc_flash_bwd_masked(const bf16* qkv, const float* key_bias, cons
                                     const float* attn_bias, long stride_b, long stride_h, hipStream_t st) {
   return flash_bwd(qkv, key_bias, out, dout, lse, dot, dqkv, B, S, H, D, scale, p, seed, salt, causal, attn_bias,
                    stride_b, stride_h, st);
+}
+
+// Grouped-query attention: Hkv <= H key/value heads (H % Hkv == 0; Hkv == 1 is multi-query,
+// Hkv == H today's layout), query head h reads K/V head h / (H / Hkv).  qkv / dqkv
+// [B*S][(H + 2*Hkv)*D]: Q head h at column h*D, K head j at (H + j)*D, V head j at
+// (H + Hkv + j)*D; dqkv is fully overwritten.  out / dout [B*S][H*D], lse / dot [B*H*S] and
+// the bias and dropout indices use the query head, so a call over K/V expanded to H heads sees
+// the same bias and drops the same elements.  Masks as in the masked entry points.  Returns -1
+// without launching for a null operand, Hkv < 1, H % Hkv != 0 or a shape the kernels do not take.
+MLC_EXPORT int mlc_flash_fwd_gqa(const bf16* qkv, const float* key_bias, bf16* out, float* lse, int B, int S, int H,
+                                 int Hkv, int D, float scale, float p, const uint32_t* seed, uint32_t salt,
+                                 int causal, const float* attn_bias, long stride_b, long stride_h, hipStream_t st) {
+  return flash_fwd_gqa(qkv, key_bias, out, lse, B, S, H, Hkv, D, scale, p, seed, salt, causal, attn_bias, stride_b,
+                       stride_h, st);
+}
+
+MLC_EXPORT int mlc_flash_bwd_gqa(const bf16* qkv, const float* key_bias, const bf16* out, const bf16* dout,
+                                 const float* lse, float* dot, bf16* dqkv, int B, int S, int H, int Hkv, int D,
+                                 float scale, float p, const uint32_t* seed, uint32_t salt, int causal,
+                                 const float* attn_bias, long stride_b, long stride_h, hipStream_t st) {
+  return flash_bwd_gqa(qkv, key_bias, out, dout, lse, dot, dqkv, B, S, H, Hkv, D, scale, p, seed, salt, causal,
+                       attn_bias, stride_b, stride_h, st);
 }
 
 // Packed variable-length batches: qkv [T][3*H*D], out / dout [T][H*D], lse / dot fp32 [H][T]

@@ -669,6 +669,24 @@ class _Lowering:
         new = self._site_node(node, site, [a['query'], a['key'], a['value']] + extra)
         self._replace([node], new)
 
+    def gqa(self, node):
+        """``grouped_query_attention(q, k, v, ...)`` (ops/gtransformer.py) -> GQASite."""
+        a = self._call_args(node, ('q', 'k', 'v', 'attn_mask', 'dropout_p', 'is_causal', 'scale'))
+        p, scale = a.get('dropout_p', 0.0), a.get('scale')
+        causal, mask = a.get('is_causal', False), a.get('attn_mask')
+        if isinstance(p, fx.Node) or isinstance(scale, fx.Node) or isinstance(causal, fx.Node):
+            raise NativeUnsupported(f'{node.name}: grouped_query_attention with a traced dropout_p / scale / '
+                                    'is_causal')
+        if mask is not None and not isinstance(mask, fx.Node):
+            raise NativeUnsupported(f'{node.name}: grouped_query_attention attn_mask {type(mask).__name__} '
+                                    '(native: a tensor)')
+        if causal and mask is not None:     # torch raises for this pair too
+            raise NativeUnsupported(f'{node.name}: grouped_query_attention with both attn_mask and is_causal')
+        site = GT.GQASite(self.net.ctx, float(p or 0.0), None if scale is None else float(scale),
+                          causal=bool(causal), has_mask=mask is not None)
+        new = self._site_node(node, site, [a['q'], a['k'], a['v']] + ([mask] if mask is not None else []))
+        self._replace([node], new)
+
     def patch_embed(self, node, m):
         """A conv with stride == kernel and no padding whose kernel is beyond the
         implicit-GEMM engine (ViT's 16x16/16 patch embedding) -> one dense GEMM."""
@@ -1159,6 +1177,8 @@ class _Lowering:
                     self.adaptive_pool(node, node.args[1] if len(node.args) > 1 else node.kwargs['output_size'])
                 elif t is F.scaled_dot_product_attention:
                     self.sdpa(node)
+                elif t is GT.grouped_query_attention:
+                    self.gqa(node)
                 elif t in (F.conv2d, torch.conv2d, F.linear, torch.matmul, torch.mm, torch.bmm, torch.addmm,
                            F.batch_norm, torch.einsum, F.conv_transpose2d, operator.matmul):
                     raise NativeUnsupported(f'{node.name}: functional {getattr(t, "__name__", t)} on module '

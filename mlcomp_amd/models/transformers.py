@@ -24,6 +24,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import register
+from ..ops.gtransformer import grouped_query_attention
 
 
 class TransformerClassifier(nn.Module):
@@ -58,17 +59,30 @@ class TransformerClassifier(nn.Module):
 
 
 class _Attention(nn.Module):
-    def __init__(self, dim, heads, attn_drop=0.0, proj_drop=0.0, causal=False):
+    """``kv_heads`` set: grouped-query attention, ``kv_heads`` key/value heads shared by groups
+    of ``heads // kv_heads`` query heads (1: multi-query) and a narrower fused projection."""
+
+    def __init__(self, dim, heads, attn_drop=0.0, proj_drop=0.0, causal=False, kv_heads=None):
         super().__init__()
         self.heads = heads
+        self.kv_heads = kv_heads
         self.causal = causal
-        self.qkv = nn.Linear(dim, dim * 3)
+        if kv_heads is not None and (kv_heads < 1 or heads % kv_heads):
+            raise ValueError(f'{heads} heads are no multiple of {kv_heads} key/value heads')
+        self.qkv = nn.Linear(dim, dim * 3 if kv_heads is None else (heads + 2 * kv_heads) * (dim // heads))
         self.attn_drop = attn_drop
         self.proj = nn.Linear(dim, dim)
         self.proj_drop = nn.Dropout(proj_drop)
 
     def forward(self, x):
         B, N, C = x.shape
+        if self.kv_heads is not None:
+            H, Hkv, D = self.heads, self.kv_heads, C // self.heads
+            q, k, v = self.qkv(x).split([H * D, Hkv * D, Hkv * D], -1)
+            x = grouped_query_attention(q.view(B, N, H, D).transpose(1, 2), k.view(B, N, Hkv, D).transpose(1, 2),
+                                        v.view(B, N, Hkv, D).transpose(1, 2),
+                                        dropout_p=self.attn_drop if self.training else 0.0, is_causal=self.causal)
+            return self.proj_drop(self.proj(x.transpose(1, 2).reshape(B, N, C)))
         qkv = self.qkv(x).reshape(B, N, 3, self.heads, C // self.heads).permute(2, 0, 3, 1, 4)
         q, k, v = qkv.unbind(0)
         if self.causal:
@@ -80,10 +94,11 @@ class _Attention(nn.Module):
 
 
 class _Block(nn.Module):
-    def __init__(self, dim, heads, mlp_ratio=4.0, drop=0.0, causal=False, attn_drop=0.0, eps=1e-6, hidden=None):
+    def __init__(self, dim, heads, mlp_ratio=4.0, drop=0.0, causal=False, attn_drop=0.0, eps=1e-6, hidden=None,
+                 kv_heads=None):
         super().__init__()
         self.norm1 = nn.LayerNorm(dim, eps=eps)
-        self.attn = _Attention(dim, heads, attn_drop=attn_drop, proj_drop=drop, causal=causal)
+        self.attn = _Attention(dim, heads, attn_drop=attn_drop, proj_drop=drop, causal=causal, kv_heads=kv_heads)
         self.norm2 = nn.LayerNorm(dim, eps=eps)
         hidden = hidden or int(dim * mlp_ratio)
         self.fc1 = nn.Linear(dim, hidden)
@@ -123,13 +138,13 @@ class VisionTransformer(nn.Module):
 
 class CausalTransformerClassifier(nn.Module):
     def __init__(self, vocab_size=30522, hidden=768, layers=12, heads=12, intermediate=3072, max_position=512,
-                 num_classes=2, dropout=0.1, eps=1e-5):
+                 num_classes=2, dropout=0.1, eps=1e-5, kv_heads=None):
         super().__init__()
         self.word = nn.Embedding(vocab_size, hidden)
         self.pos = nn.Embedding(max_position, hidden)
         self.drop = nn.Dropout(dropout)
         self.blocks = nn.Sequential(*[_Block(hidden, heads, drop=dropout, causal=True, attn_drop=dropout, eps=eps,
-                                             hidden=intermediate) for _ in range(layers)])
+                                             hidden=intermediate, kv_heads=kv_heads) for _ in range(layers)])
         self.norm = nn.LayerNorm(hidden, eps=eps)
         self.classifier = nn.Linear(hidden, num_classes)
         for m in self.modules():
@@ -153,6 +168,9 @@ TEXT_PRESETS = {'transformer-base': dict(),
 CAUSAL_PRESETS = {'transformer-causal-base': dict(),
                   'transformer-causal-tiny': dict(hidden=128, layers=2, heads=2, intermediate=512, vocab_size=1024,
                                                   max_position=128)}
+# grouped-query decoder presets (a dict of their own: CAUSAL_PRESETS' content is pinned by its tests)
+GQA_PRESETS = {'transformer-gqa-tiny': dict(hidden=256, layers=2, heads=4, kv_heads=2, intermediate=512,
+                                            vocab_size=1024, max_position=128)}
 VIT_PRESETS = {'vit-b16': dict(dim=768, depth=12, heads=12), 'vit-s16': dict(dim=384, depth=12, heads=6),
                'vit-ti16': dict(dim=192, depth=12, heads=3)}
 
@@ -166,7 +184,7 @@ def _text(name, **kw):
 
 
 def _causal(name, **kw):
-    cfg = dict(CAUSAL_PRESETS[name])
+    cfg = dict(CAUSAL_PRESETS[name] if name in CAUSAL_PRESETS else GQA_PRESETS[name])
     if 'num_labels' in kw:
         kw['num_classes'] = kw.pop('num_labels')
     cfg.update(kw)
@@ -181,10 +199,10 @@ def _vit(name, **kw):
 
 for _n in TEXT_PRESETS:
     register(_n)((lambda n: (lambda **kw: _text(n, **kw)))(_n))
-for _n in CAUSAL_PRESETS:
+for _n in list(CAUSAL_PRESETS) + list(GQA_PRESETS):
     register(_n)((lambda n: (lambda **kw: _causal(n, **kw)))(_n))
 for _n in VIT_PRESETS:
     register(_n)((lambda n: (lambda **kw: _vit(n, **kw)))(_n))
 
 __all__ = ['TransformerClassifier', 'VisionTransformer', 'CausalTransformerClassifier', 'TEXT_PRESETS',
-           'CAUSAL_PRESETS', 'VIT_PRESETS']
+           'CAUSAL_PRESETS', 'GQA_PRESETS', 'VIT_PRESETS']

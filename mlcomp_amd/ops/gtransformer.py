@@ -35,6 +35,7 @@ from types import SimpleNamespace
 from typing import List, Optional
 
 import torch
+import torch.fx
 import torch.nn as nn
 
 from . import functional as Fn
@@ -655,6 +656,65 @@ class SDPASite(Site):
             return [dqkv.view(B, S, 3 * H * D).to(dt) if needs[0] else None] + none
         d = dqkv.view(B, S, 3, H, D).permute(2, 0, 3, 1, 4)                   # [3, B, H, S, D]
         return [d[i].to(dt) if needs[i] else None for i in range(3)] + none
+
+
+def grouped_query_attention(q, k, v, attn_mask=None, dropout_p=0.0, is_causal=False, scale=None):
+    """Grouped-query attention: ``q`` [B, H, S, D], ``k`` / ``v`` [B, Hkv, S, D] with
+    ``H % Hkv == 0``; query head h attends over K/V head ``h // (H // Hkv)`` (``Hkv == 1``:
+    multi-query).  Eagerly this is ``F.scaled_dot_product_attention(..., enable_gqa=True)``;
+    under ``torch.fx`` tracing it records itself as one ``call_function`` node (however the
+    caller imported it), which the native lowering maps to :class:`GQASite` - the grouped-query
+    flash kernels."""
+    if isinstance(q, torch.fx.Proxy):
+        return q.tracer.create_proxy('call_function', grouped_query_attention, (q, k, v),
+                                     dict(attn_mask=attn_mask, dropout_p=dropout_p, is_causal=is_causal,
+                                          scale=scale))
+    return nn.functional.scaled_dot_product_attention(q, k, v, attn_mask=attn_mask, dropout_p=dropout_p,
+                                                      is_causal=is_causal, scale=scale, enable_gqa=True)
+
+
+class GQASite(SDPASite):
+    """:func:`grouped_query_attention` on the grouped-query flash kernels.  q [B, H, S, D] and
+    k, v [B, Hkv, S, D] are packed with one ``cat`` into the kernels' [B*S, (H + 2*Hkv)*D] rows
+    (Q heads | K heads | V heads); the output is a [B, H, S, D] view of the context rows, and
+    the three gradients are views of the packed ``dqkv`` (dK / dV already summed over each
+    group by the kernel).  Masks as in :class:`SDPASite`, indexed by the query head."""
+
+    def fwd(self, *inputs):
+        mask = None
+        if self.has_mask:
+            inputs, mask = inputs[:-1], inputs[-1]
+        q, k, v = inputs
+        if q.dim() != 4 or k.dim() != 4 or k.shape != v.shape:
+            raise ValueError(f'GQA site: q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)}')
+        B, H, S, D = q.shape
+        Hkv = k.shape[1]
+        if Hkv < 1 or H % Hkv != 0 or tuple(k.shape) != (B, Hkv, S, D):
+            raise ValueError(f'GQA site: q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)} (expected '
+                             '(B, H, S, D) and (B, Hkv, S, D) with H % Hkv == 0)')
+        qkv = torch.cat([t.to(torch.bfloat16) for t in (q, k, v)], 1)         # [B, H + 2*Hkv, S, D]
+        qkv = qkv.transpose(1, 2).reshape(B * S, (H + 2 * Hkv) * D)
+        scale = self.scale if self.scale is not None else 1.0 / math.sqrt(D)
+        p = self.p if self.ctx.training else 0.0
+        kb, ab = self._masks(mask, B, H, S) if mask is not None else (None, None)
+        ctx2, lse = Tx.attn_fwd_gqa(qkv, kb, B, S, H, Hkv, scale, p, _seed(self.ctx), self.salt, head_dim=D,
+                                    causal=self.causal, attn_bias=ab)
+        out = ctx2.view(B, S, H, D).transpose(1, 2)
+        saved = [qkv, lse, ctx2] + [t for t in (kb, ab) if t is not None]
+        return out, saved, (B, H, Hkv, S, D, scale, p, q.dtype, kb is not None, ab is not None)
+
+    def bwd(self, dout, saved, keep, needs):
+        qkv, lse, ctx2 = saved[:3]
+        B, H, Hkv, S, D, scale, p, dt, has_kb, has_ab = keep
+        kb = saved[3] if has_kb else None
+        ab = saved[-1] if has_ab else None
+        dctx = dout.transpose(1, 2).reshape(B * S, H * D)
+        if dctx.dtype != torch.bfloat16:
+            dctx = dctx.to(torch.bfloat16)
+        dqkv = Tx.attn_bwd_gqa(qkv, kb, dctx.contiguous(), lse, B, S, H, Hkv, scale, p, _seed(self.ctx), self.salt,
+                               head_dim=D, ctx=ctx2, causal=self.causal, attn_bias=ab)
+        d = dqkv.view(B, S, H + 2 * Hkv, D).transpose(1, 2).split([H, Hkv, Hkv], 1)
+        return [d[i].to(dt) if needs[i] else None for i in range(3)] + [None] * int(self.has_mask)
 
 
 class PatchEmbed(Site):

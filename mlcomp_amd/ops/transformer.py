@@ -473,6 +473,113 @@ def attn_bwd(qkv, key_bias, dctx, lse, B, S, H, scale, p=0.0, seed=None, salt=0,
     return dqkv.to(torch.bfloat16)
 
 
+# ---------------------------------------------------------------------------- grouped-query attention
+def _gqa_group(H: int, Hkv: int) -> int:
+    if Hkv < 1 or H % Hkv != 0:
+        raise ValueError(f'grouped-query attention: {H} query heads are no multiple of {Hkv} key/value heads')
+    return H // Hkv
+
+
+def _gqa_expand(qkv, B, S, H, Hkv, D):
+    """fp32 q [B, H, S, D] and k, v expanded to the query heads (head h reads K/V head h / G)."""
+    G = H // Hkv
+    q, k, v = qkv.float().view(B, S, H + 2 * Hkv, D).permute(0, 2, 1, 3).split([H, Hkv, Hkv], 1)
+    return q, k.repeat_interleave(G, 1), v.repeat_interleave(G, 1)
+
+
+def attn_fwd_gqa(qkv, key_bias, B, S, H, Hkv, scale, p=0.0, seed=None, salt=0, head_dim: int = 64, *,
+                 causal: bool = False, attn_bias=None):
+    """Grouped-query attention: ``Hkv`` key/value heads serve ``H`` query heads (``H % Hkv == 0``,
+    ``Hkv == 1`` is multi-query), query head h reading K/V head ``h // (H // Hkv)`` - what
+    ``F.scaled_dot_product_attention(enable_gqa=True)`` computes.  ``qkv`` [B*S, (H + 2*Hkv)*D]:
+    Q head h at column h*D, K head j at (H + j)*D, V head j at (H + Hkv + j)*D.  Returns
+    (ctx [B*S, H*D] bf16, lse [B*H*S] fp32).  ``key_bias`` / ``causal`` / ``attn_bias`` / dropout
+    as in :func:`attn_fwd`; the bias and the dropout element are indexed by the query head, so a
+    call of :func:`attn_fwd` over expanded K/V sees the same bias and drops the same elements.
+    Always the streaming kernels (``mlc_flash_fwd_gqa``)."""
+    D = head_dim
+    _gqa_group(H, Hkv)
+    if _cuda(qkv) and D not in (64, 128):
+        assert attn_supported(S, D), (S, D)
+        Dp = _pad_dim(D)
+        ctx, lse = attn_fwd_gqa(_pad_heads(qkv, B * S, 1, H + 2 * Hkv, D, Dp), key_bias, B, S, H, Hkv, scale, p, seed,
+                                salt, Dp, causal=causal, attn_bias=attn_bias)
+        return _unpad_heads(ctx, B * S, 1, H, D, Dp), lse
+    if _cuda(qkv):
+        assert attn_supported(S, D) and qkv.is_contiguous() and tuple(qkv.shape) == (B * S, (H + 2 * Hkv) * D)
+        assert key_bias is None or (key_bias.is_contiguous() and tuple(key_bias.shape) == (B, S))
+        ctx = torch.empty(B * S, H * D, device=qkv.device, dtype=torch.bfloat16)
+        lse = torch.empty(B * H * S, device=qkv.device, dtype=torch.float32)
+        ab, sb, sh = attn_bias_arg(attn_bias, B, S, H)
+        _lib.call('mlc_flash_fwd_gqa', _lib.ptr(qkv), _lib.ptr(key_bias), _lib.ptr(ctx), _lib.ptr(lse), B, S, H, Hkv,
+                  D, float(scale), float(p), _lib.ptr(seed), salt, int(bool(causal)), _lib.ptr(ab), sb, sh,
+                  _lib.stream())
+        return ctx, lse
+    q, k, v = _gqa_expand(qkv, B, S, H, Hkv, D)
+    x = _gqa_scores(q, k, key_bias, B, S, H, scale, causal, attn_bias)
+    P = torch.softmax(x, -1).nan_to_num(0.0)
+    if p > 0:
+        m = keep_mask((B, H, S, S), p, _seed_val(seed), salt)
+        P = torch.where(m, P / (1 - p), torch.zeros_like(P))
+    ctx = torch.matmul(P, v).permute(0, 2, 1, 3).reshape(B * S, H * D)
+    lse = torch.logsumexp(x, -1).reshape(-1)
+    lse = torch.where(lse == float('-inf'), torch.full_like(lse, float('inf')), lse)   # the kernels' +inf
+    return ctx.to(torch.bfloat16), lse
+
+
+def _gqa_scores(q, k, key_bias, B, S, H, scale, causal, attn_bias):
+    x = torch.matmul(q, k.transpose(-1, -2)) * scale
+    if key_bias is not None:
+        x = x + key_bias.float()[:, None, None, :]
+    if attn_bias is not None:
+        x = x + attn_bias_arg(attn_bias, B, S, H)[0]
+    if causal:
+        x = x.masked_fill(torch.ones(S, S, dtype=torch.bool, device=x.device).triu(1), float('-inf'))
+    return x
+
+
+def attn_bwd_gqa(qkv, key_bias, dctx, lse, B, S, H, Hkv, scale, p=0.0, seed=None, salt=0, head_dim: int = 64,
+                 ctx=None, *, causal: bool = False, attn_bias=None):
+    """Gradient of :func:`attn_fwd_gqa` wrt ``qkv``: dqkv [B*S, (H + 2*Hkv)*D] bf16, fully
+    written.  dK / dV of a K/V head are the sum over its group's query heads, accumulated in
+    fp32 inside one kernel block (``mlc_flash_bwd_gqa``) and rounded once.  ``ctx`` is the
+    forward output."""
+    D = head_dim
+    G = _gqa_group(H, Hkv)
+    if _cuda(qkv) and D not in (64, 128):
+        assert attn_supported(S, D) and ctx is not None, (S, D)
+        Dp = _pad_dim(D)
+        dq = attn_bwd_gqa(_pad_heads(qkv, B * S, 1, H + 2 * Hkv, D, Dp), key_bias,
+                          _pad_heads(dctx, B * S, 1, H, D, Dp), lse, B, S, H, Hkv, scale, p, seed, salt, Dp,
+                          ctx=_pad_heads(ctx, B * S, 1, H, D, Dp), causal=causal, attn_bias=attn_bias)
+        return _unpad_heads(dq, B * S, 1, H + 2 * Hkv, D, Dp)
+    if _cuda(qkv):
+        assert attn_supported(S, D) and qkv.is_contiguous() and tuple(qkv.shape) == (B * S, (H + 2 * Hkv) * D)
+        assert dctx.is_contiguous() and tuple(dctx.shape) == (B * S, H * D) and lse.numel() == B * H * S
+        assert key_bias is None or (key_bias.is_contiguous() and tuple(key_bias.shape) == (B, S))
+        assert ctx is not None and ctx.is_contiguous() and ctx.shape == dctx.shape
+        dqkv = torch.empty_like(qkv)
+        ab, sb, sh = attn_bias_arg(attn_bias, B, S, H)
+        dot = torch.empty(B * H * S, device=qkv.device, dtype=torch.float32)
+        _lib.call('mlc_flash_bwd_gqa', _lib.ptr(qkv), _lib.ptr(key_bias), _lib.ptr(ctx), _lib.ptr(dctx),
+                  _lib.ptr(lse), _lib.ptr(dot), _lib.ptr(dqkv), B, S, H, Hkv, D, float(scale), float(p),
+                  _lib.ptr(seed), salt, int(bool(causal)), _lib.ptr(ab), sb, sh, _lib.stream())
+        return dqkv
+    q, k, v = _gqa_expand(qkv, B, S, H, Hkv, D)
+    P = torch.softmax(_gqa_scores(q, k, key_bias, B, S, H, scale, causal, attn_bias), -1).nan_to_num(0.0)
+    do = dctx.float().view(B, S, H, D).permute(0, 2, 1, 3)
+    m = keep_mask((B, H, S, S), p, _seed_val(seed), salt) if p > 0 else None
+    Pd = torch.where(m, P / (1 - p), torch.zeros_like(P)) if m is not None else P
+    dPd = torch.matmul(do, v.transpose(-1, -2))
+    dP = torch.where(m, dPd / (1 - p), torch.zeros_like(dPd)) if m is not None else dPd
+    dS = scale * P * (dP - (P * dP).sum(-1, keepdim=True))
+    dq = torch.matmul(dS, k)
+    dk = torch.matmul(dS.transpose(-1, -2), q).view(B, Hkv, G, S, D).sum(2)      # the group's sum
+    dv = torch.matmul(Pd.transpose(-1, -2), do).view(B, Hkv, G, S, D).sum(2)
+    dqkv = torch.cat([dq, dk, dv], 1).permute(0, 2, 1, 3).reshape(B * S, (H + 2 * Hkv) * D)
+    return dqkv.to(torch.bfloat16)
+
+
 # ---------------------------------------------------------------------------- packed (varlen) attention
 def check_cu_seqlens(cu_seqlens, T: int, max_len: int):
     """``cu_seqlens`` (int32 [nseq_max + 1]: sequence b owns rows cu[b] .. cu[b+1]-1 of a
@@ -747,4 +854,5 @@ def dropout(x, p, seed, salt):
 
 
 __all__ = ['ln_fwd', 'ln_bwd', 'LnFinalizer', 'embed_bwd', 'embed_ln_fwd', 'embed_bwd_packed', 'cls_scatter', 'softmax_fwd', 'softmax_bwd', 'dense_fwd', 'dense_dgrad', 'dact_gelu', 'colsum_acc',
-           'dropout', 'keep_mask', 'attn_fwd_varlen', 'attn_bwd_varlen', 'check_cu_seqlens']
+           'dropout', 'keep_mask', 'attn_fwd_varlen', 'attn_bwd_varlen', 'check_cu_seqlens',
+           'attn_fwd_gqa', 'attn_bwd_gqa']
