@@ -37,6 +37,11 @@
 // per (b, K/V head, 128 keys) that streams the tiles of all its group's query heads and sums
 // their contributions in the fp32 accumulators (no atomics, one store).
 //
+// Packed grouped-query attention (the *_gqa_varlen entry points; M_VARLEN | M_GQA of the same
+// kernels): the row geometry of the packed mode (first row, length, lse / dot base from
+// cu_seqlens) with the column geometry of the grouped mode.  The dK / dV block (slot b, K/V head,
+// 128 keys) streams G * (ntl - t0) steps with ntl from its own sequence's length.
+//
 // Work split (one 256-thread block = 4 waves x 32 rows, blocks XCD-remapped so the blocks
 // sharing one (b, h) K/V slice sit on one XCD's L2):
 // * forward: a wave owns 32 queries; scores are computed transposed, S^T = K Q^T
@@ -154,7 +159,7 @@ struct Tile {
 constexpr int M_CAUSAL = 1;   // top-left aligned: query q sees keys <= q
 constexpr int M_BIAS = 2;     // additive fp32 bias[b * sb + h * sh + q * S + key], finite or -inf
 constexpr int M_VARLEN = 4;   // packed sequences: rows and length of slot b from cu_seqlens (no bias operands)
-constexpr int M_GQA = 8;      // grouped-query layout: Hkv K/V heads, qkv rows of (H + 2*Hkv)*D (never with M_VARLEN)
+constexpr int M_GQA = 8;      // grouped-query layout: Hkv K/V heads, qkv rows of (H + 2*Hkv)*D
 struct AttnBias {
   const float* p;
   long sb, sh;   // batch / head strides in elements (0 broadcasts)
@@ -183,7 +188,8 @@ __device__ __forceinline__ void load_bias_keys(f32x4 (&bv)[2][4], const float* r
 // dropout index's sequence length) and lse / dot are [H][T].
 struct VarLen {
   const int* cu;   // int32 [nseq_max + 1], device memory
-  int T;           // rows of the packed buffers; in mode M_GQA (never packed) the K/V head count Hkv
+  int T;           // rows of the packed buffers
+  int Hkv;         // mode M_GQA: the K/V head count (0 otherwise); here so that every mode's kernels share one signature
 };
 // rows of one (sequence, head): first row, length, and base of its lse / dot entries
 struct Seq {
@@ -239,7 +245,7 @@ __device__ __forceinline__ Geo geo_heavy_first(int H, int nblk, bool last_is_hea
 // Grouped-query layout (mode bit M_GQA): qkv rows are [Q: H heads | K: Hkv heads | V: Hkv heads],
 // query head h reads K/V head h / (H / Hkv).  Everything else indexed by head (out, lse, dot,
 // the bias, the dropout element) keeps the query head.  Hkv reaches fwd_kernel / dq_kernel in
-// vl.T (the mode is never packed), so the other modes' kernels keep their arguments and code.
+// vl.Hkv, so the mode combines with M_VARLEN: rows from seq_of<true>, columns from here.
 
 // ------------------------------------------------------------------ forward
 template <int D, bool DROP, int MASK>
@@ -250,11 +256,10 @@ fwd_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, bf1
   constexpr int NS = D / 16, NJ = D / 32, IMG = KT * D * 2, BUF = 2 * IMG + KT * 4;
   constexpr bool CAUSAL = (MASK & M_CAUSAL) != 0, BIAS = (MASK & M_BIAS) != 0, VARLEN = (MASK & M_VARLEN) != 0;
   constexpr bool GQA = (MASK & M_GQA) != 0;
-  static_assert(!(GQA && VARLEN), "no packed grouped-query form");
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];   // [buffer][K | V | key bias * log2e]
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, hh = lane >> 5, l32 = lane & 31;
   const Geo G = CAUSAL ? geo_heavy_first(H, nqb, true) : geo(H, nqb);
-  const int Hkv = vl.T;   // read in mode M_GQA only
+  const int Hkv = vl.Hkv;   // read in mode M_GQA only
   const int E = H * D, ld = GQA ? (H + 2 * Hkv) * D : 3 * E;
   const Seq sq = seq_of<VARLEN>(G.b, G.hd, G.bh, S, vl);
   const int L = sq.len;   // this sequence's length (S itself unless packed)
@@ -390,11 +395,10 @@ dq_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, cons
   constexpr int NS = D / 16, NJ = D / 32, IMG = KT * D * 2, BUF = 2 * IMG + KT * 4;
   constexpr bool CAUSAL = (MASK & M_CAUSAL) != 0, BIAS = (MASK & M_BIAS) != 0, VARLEN = (MASK & M_VARLEN) != 0;
   constexpr bool GQA = (MASK & M_GQA) != 0;
-  static_assert(!(GQA && VARLEN), "no packed grouped-query form");
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];   // [buffer][K | V | key bias * log2e]
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, hh = lane >> 5, l32 = lane & 31;
   const Geo G = CAUSAL ? geo_heavy_first(H, nqb, true) : geo(H, nqb);
-  const int Hkv = vl.T;   // read in mode M_GQA only
+  const int Hkv = vl.Hkv;   // read in mode M_GQA only
   const int E = H * D, ld = GQA ? (H + 2 * Hkv) * D : 3 * E;
   const Seq sq = seq_of<VARLEN>(G.b, G.hd, G.bh, S, vl);
   const int L = sq.len;
@@ -648,14 +652,19 @@ dkv_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, con
 // What depends on the head follows g (the tiles' column, lse / dot rows, the bias column
 // pointer, the dropout element's b*H + h); the causal tests depend on t alone.  With G = 1 the
 // loop is dkv_kernel's, step for step.
+// Packed (mode bit M_VARLEN): b is a slot of cu_seqlens, the block's rows start at its
+// sequence's first row and everything a length bounds - the clamped keys, the tiles' valid
+// rows, ntl and with it the stream's G * (ntl - t0) steps - takes this sequence's length L, so
+// a short sequence in a long-max_len batch streams its own tiles only.  lse / dot are [H][T]:
+// head g is T entries further on.  S stays max_len in the dropout element alone.
 template <int D, bool DROP, int MASK>
 __global__ void __launch_bounds__(NT)
 dkv_gqa_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias, const bf16* __restrict__ dout,
                const float* __restrict__ lse, const float* __restrict__ dot, bf16* __restrict__ dqkv, int S, int H,
                int Hkv, int nkb, float scale, float sl2, uint32_t thr, float inv_keep,
-               const uint32_t* __restrict__ seedp, uint32_t salt, AttnBias ab) {
+               const uint32_t* __restrict__ seedp, uint32_t salt, AttnBias ab, VarLen vl) {
   constexpr int NS = D / 16, NJ = D / 32, IMG = KT * D * 2, BUF = 2 * IMG + 2 * KT * 4;
-  constexpr bool CAUSAL = (MASK & M_CAUSAL) != 0, BIAS = (MASK & M_BIAS) != 0;
+  constexpr bool CAUSAL = (MASK & M_CAUSAL) != 0, BIAS = (MASK & M_BIAS) != 0, VARLEN = (MASK & M_VARLEN) != 0;
   // [buffer][Q image | dO image | lse*log2e [64] | dot [64]]
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, hh = lane >> 5, l32 = lane & 31;
@@ -663,13 +672,17 @@ dkv_gqa_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias,
   const Geo G = CAUSAL ? geo_heavy_first(Hkv, nkb, false) : geo(Hkv, nkb);
   const int NG = H / Hkv, E = H * D, ld = (H + 2 * Hkv) * D;
   const int h0 = G.hd * NG;   // the group's first query head
-  const bf16* Qg = qkv + (size_t)G.b * S * ld + h0 * D;
-  const bf16* Kg = qkv + (size_t)G.b * S * ld + (H + G.hd) * D;
+  const Seq sq = seq_of<VARLEN>(G.b, h0, G.b * H + h0, S, vl);   // rows and lse / dot base of (b, h0)
+  const int L = sq.len;
+  if (VARLEN && G.blk * 128 >= L) return;   // as in fwd_kernel: before any barrier or LDS traffic
+  const bf16* Qg = qkv + (size_t)sq.row0 * ld + h0 * D;
+  const bf16* Kg = qkv + (size_t)sq.row0 * ld + (H + G.hd) * D;
   const bf16* Vg = Kg + Hkv * D;
-  const bf16* dOg = dout + (size_t)G.b * S * E + h0 * D;
-  const size_t stat0 = ((size_t)G.b * H + h0) * S;   // lse / dot of (b, h0); head g is g*S further on
+  const bf16* dOg = dout + (size_t)sq.row0 * E + h0 * D;
+  const size_t stat0 = sq.stat0;                // lse / dot of (b, h0) ...
+  const size_t stat_h = VARLEN ? vl.T : S;      // ... and head g is g * stat_h further on
   const int key = G.blk * 128 + 32 * w + l32;
-  const int kc = min(key, S - 1);
+  const int kc = min(key, L - 1);
   bf16x8 kf[NS], vf[NS];
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
@@ -687,11 +700,11 @@ dkv_gqa_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias,
   Tile<D> tq, to;
   float ld_v = 0.f;   // this thread's lse / dot element of the next step (threads 0..127)
   auto fetch = [&](int g, int t) {
-    const int valid = min(KT, S - t * KT);
+    const int valid = min(KT, L - t * KT);
     tq.load(Qg + g * D + (size_t)t * KT * ld, ld, tid, valid);
     to.load(dOg + g * D + (size_t)t * KT * E, E, tid, valid);
-    // queries past S: lse = +inf makes their probabilities exactly 0
-    const size_t st = stat0 + (size_t)g * S + t * KT;
+    // queries past L: lse = +inf makes their probabilities exactly 0
+    const size_t st = stat0 + (size_t)g * stat_h + t * KT;
     if (tid < KT) ld_v = tid < valid ? lse[st + tid] * LOG2E : INFINITY;
     else if (tid < 2 * KT) ld_v = tid - KT < valid ? dot[st + tid - KT] : 0.f;
   };
@@ -701,9 +714,9 @@ dkv_gqa_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias,
     to.store(bp + IMG, tid);
     if (tid < 2 * KT) reinterpret_cast<float*>(bp + 2 * IMG)[tid] = ld_v;
   };
-  // causal: the first query tile that sees this key block (128 * blk < S, so t0 < nt)
+  // causal: the first query tile that sees this key block (128 * blk < L, so t0 < nt)
   const int t0 = CAUSAL ? 2 * G.blk : 0;
-  const int nt = (S + KT - 1) / KT;   // a partial last tile is masked
+  const int nt = (L + KT - 1) / KT;   // this sequence's tiles; a partial last tile is masked
   const int nstep = NG * (nt - t0);
   fetch(0, t0);
   put(0);
@@ -749,7 +762,7 @@ dkv_gqa_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias,
           const int r = 4 * q4 + e;
           float x = sc[i2][r] * sl2 + kbl;
           // padded queries of a tail tile re-read the last row (their lse = +inf zeroes them)
-          if constexpr (BIAS) x += bcol[(size_t)min(t * KT + q0 + e, S - 1) * S] * LOG2E;
+          if constexpr (BIAS) x += bcol[(size_t)min(t * KT + q0 + e, L - 1) * S] * LOG2E;
           if constexpr (CAUSAL)
             if (diag && t * KT + q0 + e < key) x = -INFINITY;   // p exactly 0
           const float p = __builtin_amdgcn_exp2f(x - L4[e]);
@@ -781,8 +794,8 @@ dkv_gqa_kernel(const bf16* __restrict__ qkv, const float* __restrict__ key_bias,
     g = gn;
     t = tn;
   }
-  if (key < S) {
-    bf16* dst = dqkv + ((size_t)G.b * S + key) * ld;
+  if (key < L) {
+    bf16* dst = dqkv + ((size_t)sq.row0 + key) * ld;
     store_rows<NJ>(dst + (H + G.hd) * D, dk, lane);
     store_rows<NJ>(dst + (H + Hkv + G.hd) * D, dv, lane);
   }
@@ -1424,7 +1437,7 @@ int flash_fwd(const bf16* qkv, const float* key_bias, bf16* out, float* lse, int
   const int nqb = (S + 127) / 128;
   const dim3 grid(B * H * nqb);
   const AttnBias ab = bias_arg(attn_bias, stride_b, stride_h, S);
-  const VarLen vl{nullptr, 0};
+  const VarLen vl{nullptr, 0, 0};
 #define FWD(DD, DR, MM) hipLaunchKernelGGL((fwd_kernel<DD, DR, MM>), grid, dim3(NT), 0, st, qkv, key_bias, out, lse, S, \
                                            H, nqb, scale * LOG2E, t, k, seed, salt, ab, vl)
   FLASH_DISPATCH(FWD);
@@ -1462,7 +1475,7 @@ int flash_fwd_varlen(const bf16* qkv, const int* cu, bf16* out, float* lse, int 
   const float k = p > 0.f ? 1.f / (1.f - p) : 1.f;
   if (varlen128_route(max_len, D, causal)) {
     const dim3 grid(nseq * H + TAILB);   // host integers only: fixed under graph replay
-    const VarLen vl{cu, T};
+    const VarLen vl{cu, T, 0};
     if (t)
       hipLaunchKernelGGL((fwd128_varlen_kernel<true>), grid, dim3(NT), 0, st, qkv, vl, out, lse, nseq, max_len, H,
                          scale * LOG2E, t, k, seed, salt);
@@ -1474,7 +1487,7 @@ int flash_fwd_varlen(const bf16* qkv, const int* cu, bf16* out, float* lse, int 
   const int nqb = (max_len + 127) / 128;
   const dim3 grid(nseq * H * nqb);   // from nseq_max, H and max_len only: fixed under graph replay
   const AttnBias ab = bias_arg(nullptr, 0, 0, max_len);
-  const VarLen vl{cu, T};
+  const VarLen vl{cu, T, 0};
 #define FWD(DD, DR, MM) hipLaunchKernelGGL((fwd_kernel<DD, DR, MM>), grid, dim3(NT), 0, st, qkv, nullptr, out, lse, \
                                            max_len, H, nqb, scale * LOG2E, t, k, seed, salt, ab, vl)
   VARLEN_DISPATCH(FWD);
@@ -1490,7 +1503,7 @@ int flash_bwd_varlen(const bf16* qkv, const int* cu, const bf16* out, const bf16
   const float k = p > 0.f ? 1.f / (1.f - p) : 1.f;
   if (varlen128_route(max_len, D, causal)) {   // one launch, no dot scratch
     const dim3 grid(nseq * H + TAILB);
-    const VarLen vl{cu, T};
+    const VarLen vl{cu, T, 0};
     if (t)
       hipLaunchKernelGGL((bwd128_varlen_kernel<true>), grid, dim3(NT), 0, st, qkv, vl, out, dout, lse, dqkv, nseq,
                          max_len, H, scale, scale * LOG2E, t, k, seed, salt);
@@ -1502,7 +1515,7 @@ int flash_bwd_varlen(const bf16* qkv, const int* cu, const bf16* out, const bf16
   const int nb = (max_len + 127) / 128;
   const dim3 grid(nseq * H * nb);
   const AttnBias ab = bias_arg(nullptr, 0, 0, max_len);
-  const VarLen vl{cu, T};
+  const VarLen vl{cu, T, 0};
 #define BWD(DD, DR, MM)                                                                                             \
   do {                                                                                                              \
     hipLaunchKernelGGL((dq_kernel<DD, DR, MM>), grid, dim3(NT), 0, st, qkv, nullptr, out, dout, lse, dot, dqkv,     \
@@ -1514,8 +1527,6 @@ int flash_bwd_varlen(const bf16* qkv, const int* cu, const bf16* out, const bf16
 #undef BWD
   return hipGetLastError();
 }
-#undef VARLEN_MASKS
-#undef VARLEN_DISPATCH
 
 int flash_bwd(const bf16* qkv, const float* key_bias, const bf16* out, const bf16* dout, const float* lse, float* dot,
               bf16* dqkv, int B, int S, int H, int D, float scale, float p, const uint32_t* seed, uint32_t salt,
@@ -1538,7 +1549,7 @@ int flash_bwd(const bf16* qkv, const float* key_bias, const bf16* out, const bf1
   const int nb = (S + 127) / 128;
   const dim3 grid(B * H * nb);
   const AttnBias ab = bias_arg(attn_bias, stride_b, stride_h, S);
-  const VarLen vl{nullptr, 0};
+  const VarLen vl{nullptr, 0, 0};
 #define BWD(DD, DR, MM)                                                                                              \
   do {                                                                                                               \
     hipLaunchKernelGGL((dq_kernel<DD, DR, MM>), grid, dim3(NT), 0, st, qkv, key_bias, out, dout, lse, dot, dqkv, S, H, \
@@ -1566,7 +1577,7 @@ int flash_fwd_gqa(const bf16* qkv, const float* key_bias, bf16* out, float* lse,
   const int nqb = (S + 127) / 128;
   const dim3 grid(B * H * nqb);
   const AttnBias ab = bias_arg(attn_bias, stride_b, stride_h, S);
-  const VarLen vl{nullptr, Hkv};   // M_GQA: T carries Hkv
+  const VarLen vl{nullptr, 0, Hkv};
 #define FWD(DD, DR, MM) hipLaunchKernelGGL((fwd_kernel<DD, DR, MM | M_GQA>), grid, dim3(NT), 0, st, qkv, key_bias, out, \
                                            lse, S, H, nqb, scale * LOG2E, t, k, seed, salt, ab, vl)
   FLASH_DISPATCH(FWD);
@@ -1586,18 +1597,63 @@ int flash_bwd_gqa(const bf16* qkv, const float* key_bias, const bf16* out, const
   const int nb = (S + 127) / 128;
   const dim3 grid(B * H * nb), grid_kv(B * Hkv * nb);
   const AttnBias ab = bias_arg(attn_bias, stride_b, stride_h, S);
-  const VarLen vl{nullptr, Hkv};   // M_GQA: T carries Hkv
+  const VarLen vl{nullptr, 0, Hkv};
 #define BWD(DD, DR, MM)                                                                                               \
   do {                                                                                                                \
     hipLaunchKernelGGL((dq_kernel<DD, DR, MM | M_GQA>), grid, dim3(NT), 0, st, qkv, key_bias, out, dout, lse, dot,    \
                        dqkv, S, H, nb, scale, scale * LOG2E, t, k, seed, salt, ab, vl);                          \
     hipLaunchKernelGGL((dkv_gqa_kernel<DD, DR, MM>), grid_kv, dim3(NT), 0, st, qkv, key_bias, dout, lse, dot, dqkv,   \
-                       S, H, Hkv, nb, scale, scale * LOG2E, t, k, seed, salt, ab);                                    \
+                       S, H, Hkv, nb, scale, scale * LOG2E, t, k, seed, salt, ab, vl);                                \
   } while (0)
   FLASH_DISPATCH(BWD);
 #undef BWD
   return hipGetLastError();
 }
+
+// Packed grouped-query calls: the packed calls' grids (host integers only) over the grouped
+// calls' kernels, always streaming.  dK / dV: nseq * Hkv * ceil(max_len / 128) blocks.
+int flash_fwd_gqa_varlen(const bf16* qkv, const int* cu, bf16* out, float* lse, int T, int nseq, int max_len, int H,
+                         int Hkv, int D, float scale, float p, const uint32_t* seed, uint32_t salt, int causal,
+                         hipStream_t st) {
+  if (!qkv || !out || !lse || !varlen_shape_ok(cu, T, nseq, max_len, H, D) || !gqa_heads_ok(H, Hkv)) return -1;
+  const uint32_t t = p > 0.f ? drop_threshold(p) : 0u;
+  const float k = p > 0.f ? 1.f / (1.f - p) : 1.f;
+  const int nqb = (max_len + 127) / 128;
+  const dim3 grid(nseq * H * nqb);
+  const AttnBias ab = bias_arg(nullptr, 0, 0, max_len);
+  const VarLen vl{cu, T, Hkv};
+#define FWD(DD, DR, MM) hipLaunchKernelGGL((fwd_kernel<DD, DR, MM | M_GQA>), grid, dim3(NT), 0, st, qkv, nullptr, out, \
+                                           lse, max_len, H, nqb, scale * LOG2E, t, k, seed, salt, ab, vl)
+  VARLEN_DISPATCH(FWD);
+#undef FWD
+  return hipGetLastError();
+}
+
+int flash_bwd_gqa_varlen(const bf16* qkv, const int* cu, const bf16* out, const bf16* dout, const float* lse,
+                         float* dot, bf16* dqkv, int T, int nseq, int max_len, int H, int Hkv, int D, float scale,
+                         float p, const uint32_t* seed, uint32_t salt, int causal, hipStream_t st) {
+  if (!qkv || !out || !dout || !lse || !dot || !dqkv || !varlen_shape_ok(cu, T, nseq, max_len, H, D) ||
+      !gqa_heads_ok(H, Hkv))
+    return -1;
+  const uint32_t t = p > 0.f ? drop_threshold(p) : 0u;
+  const float k = p > 0.f ? 1.f / (1.f - p) : 1.f;
+  const int nb = (max_len + 127) / 128;
+  const dim3 grid(nseq * H * nb), grid_kv(nseq * Hkv * nb);
+  const AttnBias ab = bias_arg(nullptr, 0, 0, max_len);
+  const VarLen vl{cu, T, Hkv};
+#define BWD(DD, DR, MM)                                                                                               \
+  do {                                                                                                                \
+    hipLaunchKernelGGL((dq_kernel<DD, DR, MM | M_GQA>), grid, dim3(NT), 0, st, qkv, nullptr, out, dout, lse, dot,     \
+                       dqkv, max_len, H, nb, scale, scale * LOG2E, t, k, seed, salt, ab, vl);                         \
+    hipLaunchKernelGGL((dkv_gqa_kernel<DD, DR, MM>), grid_kv, dim3(NT), 0, st, qkv, nullptr, dout, lse, dot, dqkv,    \
+                       max_len, H, Hkv, nb, scale, scale * LOG2E, t, k, seed, salt, ab, vl);                          \
+  } while (0)
+  VARLEN_DISPATCH(BWD);
+#undef BWD
+  return hipGetLastError();
+}
+#undef VARLEN_MASKS
+#undef VARLEN_DISPATCH
 #undef FLASH_MASKS
 #undef FLASH_DISPATCH
 
@@ -1689,6 +1745,29 @@ MLC_EXPORT int mlc_flash_bwd_varlen(const bf16* qkv, const int* cu_seqlens, cons
                                     int causal, hipStream_t st) {
   return flash_bwd_varlen(qkv, cu_seqlens, out, dout, lse, dot, dqkv, T, nseq_max, max_len, H, D, scale, p, seed,
                           salt, causal, st);
+}
+
+// Packed grouped-query attention: the cu_seqlens contract of the packed entry points (device
+// vector, lengths clamped on the device, grid from nseq_max / H / Hkv / max_len only, early exit
+// of blocks past their sequence, rows of no sequence not written: pass zero-filled out / lse /
+// dqkv) with the layout of the grouped entry points: qkv / dqkv [T][(H + 2*Hkv)*D], out / dout
+// [T][H*D], lse / dot fp32 [H][T] at h*T + row with h the query head.  Dropout drops element
+// ((b*H + h)*max_len + q)*max_len + key.  No bias operands; always the streaming kernels (no
+// whole-sequence route, whatever max_len).  Returns -1 without launching for a null operand,
+// Hkv < 1, H % Hkv != 0 or a shape the packed entry points refuse.
+MLC_EXPORT int mlc_flash_fwd_gqa_varlen(const bf16* qkv, const int* cu_seqlens, bf16* out, float* lse, int T,
+                                        int nseq_max, int max_len, int H, int Hkv, int D, float scale, float p,
+                                        const uint32_t* seed, uint32_t salt, int causal, hipStream_t st) {
+  return flash_fwd_gqa_varlen(qkv, cu_seqlens, out, lse, T, nseq_max, max_len, H, Hkv, D, scale, p, seed, salt,
+                              causal, st);
+}
+
+MLC_EXPORT int mlc_flash_bwd_gqa_varlen(const bf16* qkv, const int* cu_seqlens, const bf16* out, const bf16* dout,
+                                        const float* lse, float* dot, bf16* dqkv, int T, int nseq_max, int max_len,
+                                        int H, int Hkv, int D, float scale, float p, const uint32_t* seed,
+                                        uint32_t salt, int causal, hipStream_t st) {
+  return flash_bwd_gqa_varlen(qkv, cu_seqlens, out, dout, lse, dot, dqkv, T, nseq_max, max_len, H, Hkv, D, scale, p,
+                              seed, salt, causal, st);
 }
 
 // 1: a packed call of this shape runs the whole-sequence pair (fwd128_varlen / bwd128_varlen)

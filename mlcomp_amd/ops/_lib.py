@@ -91,6 +91,8 @@ _SIGS = {
     'mlc_flash_bwd_gqa': [vp] * 7 + [i32] * 5 + [f32, f32, vp, u32, i32, vp, i64, i64, vp],
     'mlc_flash_fwd_varlen': [vp] * 4 + [i32] * 5 + [f32, f32, vp, u32, i32, vp],
     'mlc_flash_bwd_varlen': [vp] * 7 + [i32] * 5 + [f32, f32, vp, u32, i32, vp],
+    'mlc_flash_fwd_gqa_varlen': [vp] * 4 + [i32] * 6 + [f32, f32, vp, u32, i32, vp],
+    'mlc_flash_bwd_gqa_varlen': [vp] * 7 + [i32] * 6 + [f32, f32, vp, u32, i32, vp],
     'mlc_flash_varlen128_ok': [i32, i32, i32],
     'mlc_flash_varlen128_get_set': [i32, i32],
     'mlc_flash_bwd128': [i32],

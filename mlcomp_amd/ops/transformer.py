@@ -718,6 +718,100 @@ def attn_bwd_varlen(qkv, cu_seqlens, max_len, dctx, lse, H, scale, p=0.0, seed=N
     return dqkv.to(torch.bfloat16)
 
 
+# ---------------------------------------------------------------------------- packed grouped-query attention
+def attn_fwd_gqa_varlen(qkv, cu_seqlens, max_len, H, Hkv, scale, p=0.0, seed=None, salt=0, head_dim: int = 64, *,
+                        causal: bool = False, key_bias=None, attn_bias=None):
+    """Grouped-query attention over packed sequences: the rows of :func:`attn_fwd_varlen`
+    (``cu_seqlens`` int32 [nseq_max + 1], every length <= ``max_len``) with the columns of
+    :func:`attn_fwd_gqa`: ``qkv`` [T, (H + 2*Hkv)*D], Q head h at column h*D, K head j at
+    (H + j)*D, V head j at (H + Hkv + j)*D.  Returns (ctx [T, H*D] bf16, lse [H*T] fp32, index
+    h*T + row with h the query head).  Rows of no sequence come back as exact zeros.  Dropout
+    drops element ((b*H + h)*max_len + q)*max_len + key, what the padded grouped call at
+    S = max_len drops.  Bias operands are refused (ValueError).  Always the streaming kernels
+    (``mlc_flash_fwd_gqa_varlen``), whatever ``max_len``.  Rotary embeddings on a packed batch:
+    ``rope_qkv_(pos_ids=)`` on ``qkv`` first."""
+    _no_bias_with_cu(key_bias, attn_bias)
+    _gqa_group(H, Hkv)
+    D, T = head_dim, qkv.shape[0]
+    check_cu_seqlens(cu_seqlens, T, max_len)
+    nseq = cu_seqlens.numel() - 1
+    if _cuda(qkv) and D not in (64, 128):
+        assert attn_supported(max_len, D), (max_len, D)
+        Dp = _pad_dim(D)
+        ctx, lse = attn_fwd_gqa_varlen(_pad_heads(qkv, T, 1, H + 2 * Hkv, D, Dp), cu_seqlens, max_len, H, Hkv, scale,
+                                       p, seed, salt, Dp, causal=causal)
+        return _unpad_heads(ctx, T, 1, H, D, Dp), lse
+    if _cuda(qkv):
+        assert attn_supported(max_len, D) and qkv.is_contiguous() and tuple(qkv.shape) == (T, (H + 2 * Hkv) * D)
+        cu = cu_seqlens.to(device=qkv.device, dtype=torch.int32).contiguous()
+        ctx = torch.zeros(T, H * D, device=qkv.device, dtype=torch.bfloat16)
+        lse = torch.zeros(H * T, device=qkv.device, dtype=torch.float32)
+        _lib.call('mlc_flash_fwd_gqa_varlen', _lib.ptr(qkv), _lib.ptr(cu), _lib.ptr(ctx), _lib.ptr(lse), T, nseq,
+                  int(max_len), H, Hkv, D, float(scale), float(p), _lib.ptr(seed), salt, int(bool(causal)),
+                  _lib.stream())
+        return ctx, lse
+    ctx = torch.zeros(T, H * D)
+    lse = torch.zeros(H, T)
+    for b, c0, c1 in _seq_slices(cu_seqlens):
+        L = c1 - c0
+        q, k, v = _gqa_expand(qkv[c0:c1], 1, L, H, Hkv, D)
+        x = _gqa_scores(q, k, None, 1, L, H, scale, causal, None)
+        P = torch.softmax(x, -1)
+        if p > 0:
+            P = torch.where(_seq_keep(b, H, L, max_len, p, seed, salt)[None], P / (1 - p), torch.zeros_like(P))
+        ctx[c0:c1] = torch.matmul(P, v).permute(0, 2, 1, 3).reshape(L, H * D)
+        lse[:, c0:c1] = torch.logsumexp(x, -1)[0]
+    return ctx.to(torch.bfloat16), lse.reshape(-1)
+
+
+def attn_bwd_gqa_varlen(qkv, cu_seqlens, max_len, dctx, lse, H, Hkv, scale, p=0.0, seed=None, salt=0,
+                        head_dim: int = 64, ctx=None, *, causal: bool = False, key_bias=None, attn_bias=None):
+    """Gradient of :func:`attn_fwd_gqa_varlen` wrt ``qkv``: dqkv [T, (H + 2*Hkv)*D] bf16, exact
+    zeros in the rows of no sequence.  dK / dV of a K/V head are the sum over its group's query
+    heads, accumulated in fp32 inside one kernel block per (sequence, K/V head, 128 keys) that
+    streams only its own sequence's tiles (``mlc_flash_bwd_gqa_varlen``).  ``ctx`` is the
+    forward output."""
+    _no_bias_with_cu(key_bias, attn_bias)
+    G = _gqa_group(H, Hkv)
+    D, T = head_dim, qkv.shape[0]
+    check_cu_seqlens(cu_seqlens, T, max_len)
+    nseq = cu_seqlens.numel() - 1
+    if _cuda(qkv) and D not in (64, 128):
+        assert attn_supported(max_len, D) and ctx is not None, (max_len, D)
+        Dp = _pad_dim(D)
+        dq = attn_bwd_gqa_varlen(_pad_heads(qkv, T, 1, H + 2 * Hkv, D, Dp), cu_seqlens, max_len,
+                                 _pad_heads(dctx, T, 1, H, D, Dp), lse, H, Hkv, scale, p, seed, salt, Dp,
+                                 ctx=_pad_heads(ctx, T, 1, H, D, Dp), causal=causal)
+        return _unpad_heads(dq, T, 1, H + 2 * Hkv, D, Dp)
+    if _cuda(qkv):
+        assert attn_supported(max_len, D) and qkv.is_contiguous() and tuple(qkv.shape) == (T, (H + 2 * Hkv) * D)
+        assert dctx.is_contiguous() and tuple(dctx.shape) == (T, H * D) and lse.numel() == H * T
+        assert ctx is not None and ctx.is_contiguous() and ctx.shape == dctx.shape
+        cu = cu_seqlens.to(device=qkv.device, dtype=torch.int32).contiguous()
+        dqkv = torch.zeros_like(qkv)
+        dot = torch.empty(H * T, device=qkv.device, dtype=torch.float32)
+        _lib.call('mlc_flash_bwd_gqa_varlen', _lib.ptr(qkv), _lib.ptr(cu), _lib.ptr(ctx), _lib.ptr(dctx),
+                  _lib.ptr(lse), _lib.ptr(dot), _lib.ptr(dqkv), T, nseq, int(max_len), H, Hkv, D, float(scale),
+                  float(p), _lib.ptr(seed), salt, int(bool(causal)), _lib.stream())
+        return dqkv
+    dqkv = torch.zeros(T, (H + 2 * Hkv) * D)
+    for b, c0, c1 in _seq_slices(cu_seqlens):
+        L = c1 - c0
+        q, k, v = _gqa_expand(qkv[c0:c1], 1, L, H, Hkv, D)
+        P = torch.softmax(_gqa_scores(q, k, None, 1, L, H, scale, causal, None), -1)
+        do = dctx[c0:c1].float().view(1, L, H, D).permute(0, 2, 1, 3)
+        m = _seq_keep(b, H, L, max_len, p, seed, salt)[None] if p > 0 else None
+        Pd = torch.where(m, P / (1 - p), torch.zeros_like(P)) if m is not None else P
+        dPd = torch.matmul(do, v.transpose(-1, -2))
+        dP = torch.where(m, dPd / (1 - p), torch.zeros_like(dPd)) if m is not None else dPd
+        dS = scale * P * (dP - (P * dP).sum(-1, keepdim=True))
+        dq = torch.matmul(dS, k)
+        dk = torch.matmul(dS.transpose(-1, -2), q).view(1, Hkv, G, L, D).sum(2)      # the group's sum
+        dv = torch.matmul(Pd.transpose(-1, -2), do).view(1, Hkv, G, L, D).sum(2)
+        dqkv[c0:c1] = torch.cat([dq, dk, dv], 1).permute(0, 2, 1, 3).reshape(L, (H + 2 * Hkv) * D)
+    return dqkv.to(torch.bfloat16)
+
+
 # ---------------------------------------------------------------------------- dense layers
 _WS = {}
 _WS_OLD = []   # superseded buffers stay alive: a captured graph may still point at them
@@ -984,5 +1078,5 @@ def swiglu_bwd(gu, dh, out=None):
 
 __all__ = ['ln_fwd', 'ln_bwd', 'LnFinalizer', 'embed_bwd', 'embed_ln_fwd', 'embed_bwd_packed', 'cls_scatter', 'softmax_fwd', 'softmax_bwd', 'dense_fwd', 'dense_dgrad', 'dact_gelu', 'colsum_acc',
            'dropout', 'keep_mask', 'attn_fwd_varlen', 'attn_bwd_varlen', 'check_cu_seqlens',
-           'attn_fwd_gqa', 'attn_bwd_gqa', 'rope_table', 'rope_qkv_', 'rms_fwd', 'rms_bwd', 'swiglu_fwd', 'swiglu_bwd',
+           'attn_fwd_gqa', 'attn_bwd_gqa', 'attn_fwd_gqa_varlen', 'attn_bwd_gqa_varlen', 'rope_table', 'rope_qkv_', 'rms_fwd', 'rms_bwd', 'swiglu_fwd', 'swiglu_bwd',
            'decoder_native', 'set_decoder_native']
