@@ -70,6 +70,9 @@ _SIGS = {
     'mlc_rms_bwd': [vp] * 7 + [i32, i32, vp],
     'mlc_swiglu_fwd': [vp, vp, i32, i32, vp],
     'mlc_swiglu_bwd': [vp] * 3 + [i32, i32, vp],
+    'mlc_lmhead_splits': [i32, i32, i32],
+    'mlc_lmhead_lse': [vp] * 6 + [i32] * 4 + [i64, vp],
+    'mlc_lmhead_dlogits': [vp] * 6 + [i32] * 4 + [i64, vp],
     'mlc_softmax_fwd': [vp] * 4 + [i64, i32, i32, f32, f32, vp, u32, vp],
     'mlc_softmax_bwd': [vp] * 3 + [i64, i32, f32, f32, vp, u32, vp],
     'mlc_linear_wgrad_bias': [vp] * 4 + [i32] * 7 + [vp, i64, vp],

@@ -1076,7 +1076,131 @@ def swiglu_bwd(gu, dh, out=None):
     return out
 
 
-__all__ = ['ln_fwd', 'ln_bwd', 'LnFinalizer', 'embed_bwd', 'embed_ln_fwd', 'embed_bwd_packed', 'cls_scatter', 'softmax_fwd', 'softmax_bwd', 'dense_fwd', 'dense_dgrad', 'dact_gelu', 'colsum_acc',
+# ---------------------------------------------------------------------------- language-model head + loss
+# csrc/kernels/lmhead.hip: softmax cross-entropy over z = h w^T with the logits kept in MFMA
+# accumulators.  The backward writes one bf16 dlogits chunk at a time into a cached buffer and
+# hands it to the existing dgrad / wgrad GEMMs.
+_LM_DL = {}
+LM_DL_BYTES = 256 << 20     # target size of the dlogits chunk buffer
+
+
+def _lm_shapes(h, w, labels):
+    T, K = h.shape
+    V = w.shape[0]
+    if w.dim() != 2 or w.shape[1] != K or tuple(labels.shape) != (T,):
+        raise ValueError(f'lm head: h {tuple(h.shape)}, w {tuple(w.shape)}, labels {tuple(labels.shape)} '
+                         '(expected [T, K], [V, K], [T])')
+    if T < 1 or K % 64 or V % 8:
+        raise ValueError(f'lm head: T = {T}, K = {K}, V = {V}; the kernels need T >= 1, K % 64 == 0 and V % 8 == 0')
+    assert h.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and labels.dtype == torch.int64
+    assert h.is_contiguous() and w.is_contiguous() and labels.is_contiguous()
+    return T, K, V
+
+
+def _lm_logits(h, w, labels, ignore_index):
+    """fp32 twin: logits, lse, clamped labels and the ignored-row mask"""
+    z = h.float() @ w.float().t()
+    ign = labels == ignore_index
+    lab = torch.where(ign, torch.zeros_like(labels), labels.clamp(0, w.shape[0] - 1))
+    return z, torch.logsumexp(z, 1), lab, ign
+
+
+def lm_loss_fwd(h, w, labels, ignore_index=-100, splits=0):
+    """Per-token cross-entropy of the logits h w^T without storing them: (nll, lse), fp32 [T].
+    h [T, K] bf16, w [V, K] bf16, labels int64 [T] (``mlc_lmhead_lse``: K % 64 == 0, V % 8 == 0).
+    ``nll`` is 0 where the label equals ``ignore_index``.  ``splits``: vocabulary splits per row
+    tile, 0 = enough to fill the chip."""
+    T, K, V = _lm_shapes(h, w, labels)
+    if _cuda(h):
+        sp = _lib.load().mlc_lmhead_splits(T, V, int(splits))
+        part = torch.empty((2 * sp + 1) * T, device=h.device, dtype=torch.float32)
+        nll, lse = (torch.empty(T, device=h.device, dtype=torch.float32) for _ in range(2))
+        _lib.call('mlc_lmhead_lse', _lib.ptr(h), _lib.ptr(w), _lib.ptr(labels), _lib.ptr(part), _lib.ptr(lse),
+                  _lib.ptr(nll), T, V, K, sp, int(ignore_index), _lib.stream())
+        return nll, lse
+    z, lse, lab, ign = _lm_logits(h, w, labels, ignore_index)
+    nll = lse - z.gather(1, lab[:, None])[:, 0]
+    return torch.where(ign, torch.zeros_like(nll), nll), lse
+
+
+def lm_dlogits_buffer(device, rows: int, V: int) -> torch.Tensor:
+    """The bf16 [rows, V] dlogits chunk, cached per device (and stream role / capture scope) like
+    :func:`gemm_workspace`; superseded buffers stay alive for captured graphs."""
+    from .functional import workspace_key, workspace_store
+    key = workspace_key(device)
+    store = workspace_store(_LM_DL)
+    buf = store.get(key)
+    if buf is None or buf.numel() < rows * V:
+        if buf is not None:
+            _WS_OLD.append(buf)
+        buf = store[key] = torch.empty(rows * V, device=device, dtype=torch.bfloat16)
+    return buf[:rows * V].view(rows, V)
+
+
+def lm_loss_bwd(h, w, labels, lse, dnll, dw, ignore_index=-100, chunk_rows=None):
+    """Backward of :func:`lm_loss_fwd`: returns dh [T, K] bf16 and ACCUMULATES (+=) the weight
+    gradient into ``dw`` [V, K] fp32.  ``dnll`` fp32 [T] is the gradient arriving at each row's
+    nll.  Rows go through in chunks of ``chunk_rows`` (default: the multiple of 128 that keeps the
+    chunk near 256 MB): ``mlc_lmhead_dlogits`` recomputes the chunk's logits and writes
+    (softmax - onehot) * dnll as bf16 into one reused buffer, then ``dense_dgrad`` and
+    ``linear_wgrad`` consume it."""
+    from . import functional as Fn
+    T, K, V = _lm_shapes(h, w, labels)
+    if chunk_rows is None:
+        chunk_rows = max(128, LM_DL_BYTES // (2 * V) // 128 * 128)
+    chunk_rows = min(int(chunk_rows), T)
+    dh = torch.empty(T, K, device=h.device, dtype=torch.bfloat16)
+    dl = lm_dlogits_buffer(h.device, chunk_rows, V) if _cuda(h) else None
+    for r0 in range(0, T, chunk_rows):
+        n = min(chunk_rows, T - r0)
+        hc, lc = h[r0:r0 + n], labels[r0:r0 + n]
+        if _cuda(h):
+            g = dl[:n]
+            _lib.call('mlc_lmhead_dlogits', _lib.ptr(hc), _lib.ptr(w), _lib.ptr(lc), _lib.ptr(lse[r0:r0 + n]),
+                      _lib.ptr(dnll[r0:r0 + n]), _lib.ptr(g), n, V, K, 0, int(ignore_index), _lib.stream())
+        else:
+            z, _, lab, ign = _lm_logits(hc, w, lc, ignore_index)
+            p = torch.exp(z - lse[r0:r0 + n, None])
+            p.scatter_add_(1, lab[:, None], -torch.ones(n, 1))
+            g = (p * torch.where(ign, torch.zeros(n), dnll[r0:r0 + n])[:, None]).to(torch.bfloat16)
+        dh[r0:r0 + n] = dense_dgrad(g, w)
+        Fn.linear_wgrad(g, hc, out=dw, accumulate=True)
+    return dh
+
+
+class _LmHeadLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, hidden, weight, labels, ignore_index, mean):
+        h = hidden.reshape(-1, hidden.shape[-1]).to(torch.bfloat16).contiguous()
+        w = weight.to(torch.bfloat16).contiguous()
+        lab = labels.reshape(-1).contiguous()
+        nll, lse = lm_loss_fwd(h, w, lab, ignore_index)
+        # the normaliser stays on the device: no host sync, capturable
+        scale = 1.0 / (lab != ignore_index).sum().clamp_min(1).float() if mean else torch.ones((), device=h.device)
+        ctx.save_for_backward(h, w, lab, lse, scale)
+        ctx.ignore_index, ctx.hshape, ctx.dtypes = ignore_index, hidden.shape, (hidden.dtype, weight.dtype)
+        return nll.sum() * scale
+
+    @staticmethod
+    def backward(ctx, dloss):
+        h, w, lab, lse, scale = ctx.saved_tensors
+        dnll = (dloss.float() * scale).expand(h.shape[0]).contiguous()
+        dw = torch.zeros(w.shape, device=w.device, dtype=torch.float32)
+        dh = lm_loss_bwd(h, w, lab, lse, dnll, dw, ctx.ignore_index)
+        return dh.view(ctx.hshape).to(ctx.dtypes[0]), dw.to(ctx.dtypes[1]), None, None, None
+
+
+def lm_head_loss(hidden, weight, labels, ignore_index=-100, reduction='mean'):
+    """Cross-entropy of ``hidden @ weight.T`` against ``labels`` as a 0-dim fp32 loss, differentiable
+    in ``hidden`` ([..., K], flattened to rows) and ``weight`` ([V, K]; fp32 master weights are cast to
+    bf16), on the fused kernels: :func:`lm_loss_fwd` / :func:`lm_loss_bwd`.  ``reduction``: 'mean'
+    over the rows whose label is not ``ignore_index`` (counted on the device), or 'sum'."""
+    if reduction not in ('mean', 'sum'):
+        raise ValueError(f"lm_head_loss: reduction {reduction!r} (expected 'mean' or 'sum')")
+    return _LmHeadLoss.apply(hidden, weight, labels, int(ignore_index), reduction == 'mean')
+
+
+__all__ = ['lm_loss_fwd', 'lm_loss_bwd', 'lm_head_loss', 'ln_fwd', 'ln_bwd', 'LnFinalizer', 'embed_bwd', 'embed_ln_fwd', 'embed_bwd_packed', 'cls_scatter', 'softmax_fwd', 'softmax_bwd', 'dense_fwd', 'dense_dgrad', 'dact_gelu', 'colsum_acc',
            'dropout', 'keep_mask', 'attn_fwd_varlen', 'attn_bwd_varlen', 'check_cu_seqlens',
            'attn_fwd_gqa', 'attn_bwd_gqa', 'attn_fwd_gqa_varlen', 'attn_bwd_gqa_varlen', 'rope_table', 'rope_qkv_', 'rms_fwd', 'rms_bwd', 'swiglu_fwd', 'swiglu_bwd',
            'decoder_native', 'set_decoder_native']
