@@ -73,6 +73,10 @@ _SIGS = {
     'mlc_lmhead_splits': [i32, i32, i32],
     'mlc_lmhead_lse': [vp] * 6 + [i32] * 4 + [i64, vp],
     'mlc_lmhead_dlogits': [vp] * 6 + [i32] * 4 + [i64, vp],
+    # single-token attention over a K/V cache (attn_decode.hip)
+    'mlc_attn_decode_splits': [i32, i32, i32, i32],
+    'mlc_attn_decode': [vp, i64] + [vp] * 5 + [i32] * 7 + [f32, vp],
+    'mlc_kv_append': [vp, i64, vp, vp] + [i32] * 5 + [vp],
     'mlc_softmax_fwd': [vp] * 4 + [i64, i32, i32, f32, f32, vp, u32, vp],
     'mlc_softmax_bwd': [vp] * 3 + [i64, i32, f32, f32, vp, u32, vp],
     'mlc_linear_wgrad_bias': [vp] * 4 + [i32] * 7 + [vp, i64, vp],

@@ -1200,7 +1200,111 @@ def lm_head_loss(hidden, weight, labels, ignore_index=-100, reduction='mean'):
     return _LmHeadLoss.apply(hidden, weight, labels, int(ignore_index), reduction == 'mean')
 
 
-__all__ = ['lm_loss_fwd', 'lm_loss_bwd', 'lm_head_loss', 'ln_fwd', 'ln_bwd', 'LnFinalizer', 'embed_bwd', 'embed_ln_fwd', 'embed_bwd_packed', 'cls_scatter', 'softmax_fwd', 'softmax_bwd', 'dense_fwd', 'dense_dgrad', 'dact_gelu', 'colsum_acc',
+# ---------------------------------------------------------------------------- single-token attention over a K/V cache
+# csrc/kernels/attn_decode.hip: one new query row per sequence against kv_cache [B, Smax, 2*Hkv*D]
+# (K head j of a position at column j*D, V head j at (Hkv + j)*D: the tail of a packed qkv row).
+# The lengths are device data, so one captured graph serves every step of a generation.
+_DEC_PART = {}
+
+
+def _decode_shapes(kv_cache, seq_lens, H, Hkv, D, what):
+    G = _gqa_group(H, Hkv)
+    if G > 16:
+        raise ValueError(f'{what}: {G} query heads per key/value head (the kernel serves at most 16)')
+    if D not in (64, 128):
+        raise ValueError(f'{what}: head_dim {D} (expected 64 or 128)')
+    if kv_cache.dim() != 3 or kv_cache.shape[1] < 1 or kv_cache.shape[2] != 2 * Hkv * D:
+        raise ValueError(f'{what}: kv_cache {tuple(kv_cache.shape)} (expected [B, Smax >= 1, 2*Hkv*D = {2 * Hkv * D}])')
+    if kv_cache.dtype != torch.bfloat16 or seq_lens.dtype != torch.int32:
+        raise ValueError(f'{what}: kv_cache {kv_cache.dtype}, seq_lens {seq_lens.dtype} (expected bfloat16, int32)')
+    if tuple(seq_lens.shape) != (kv_cache.shape[0],) or not kv_cache.is_contiguous() or not seq_lens.is_contiguous():
+        raise ValueError(f'{what}: seq_lens {tuple(seq_lens.shape)} for kv_cache {tuple(kv_cache.shape)} '
+                         '(expected [B], both contiguous)')
+    return kv_cache.shape[0], kv_cache.shape[1]
+
+
+def decode_partials(device, n: int) -> torch.Tensor:
+    """The fp32 partials of the split decode kernel, cached per device (and stream role / capture
+    scope) like :func:`gemm_workspace`; superseded buffers stay alive for captured graphs."""
+    from .functional import workspace_key, workspace_store
+    key = workspace_key(device)
+    store = workspace_store(_DEC_PART)
+    buf = store.get(key)
+    if buf is None or buf.numel() < n:
+        if buf is not None:
+            _WS_OLD.append(buf)
+        buf = store[key] = torch.empty(n, device=device, dtype=torch.float32)
+    return buf
+
+
+def attn_decode_gqa(q, kv_cache, seq_lens, H, Hkv, scale, head_dim: int = 64, *, max_len=None, splits: int = 0,
+                    out=None):
+    """One decode step of grouped-query attention: query row b (``q`` [B, H*D] bf16, unit inner
+    stride, any row stride: the Q columns of the step's packed projection output pass as a view)
+    against the first ``seq_lens[b]`` positions of ``kv_cache`` [B, Smax, 2*Hkv*D] bf16, query head h
+    reading K/V head ``h // (H // Hkv)``.  ``seq_lens`` int32 [B] stays on the device.  Returns
+    (ctx [B, H*D] bf16, lse [B, H] fp32 = log sum exp(scale * q.k)); a length of 0 gives ctx = 0 and
+    lse = -inf; cache rows at or past the length are never used (they may hold NaN).  ``max_len``: a
+    host-side upper bound of the lengths (default Smax) that sizes the key splits; ``splits``: 0 =
+    chosen to fill the chip (``mlc_attn_decode_splits``).  ``out``: a contiguous [B, H*D] bf16 ctx."""
+    D = head_dim
+    B, Smax = _decode_shapes(kv_cache, seq_lens, H, Hkv, D, 'attn_decode_gqa')
+    if q.dim() != 2 or tuple(q.shape) != (B, H * D) or q.dtype != torch.bfloat16 or q.stride(1) != 1:
+        raise ValueError(f'attn_decode_gqa: q {tuple(q.shape)} {q.dtype} strides {tuple(q.stride())} '
+                         f'(expected [{B}, {H * D}] bfloat16 with unit inner stride)')
+    if out is not None and (tuple(out.shape) != (B, H * D) or out.dtype != torch.bfloat16 or not out.is_contiguous()):
+        raise ValueError(f'attn_decode_gqa: out {tuple(out.shape)} {out.dtype} (expected contiguous [{B}, {H * D}] bfloat16)')
+    max_len = Smax if max_len is None else max(1, min(int(max_len), Smax))
+    ctx = out if out is not None else torch.empty(B, H * D, device=q.device, dtype=torch.bfloat16)
+    if _cuda(q):
+        if B > 1 and q.stride(0) % 8 or q.data_ptr() % 16:
+            raise ValueError('attn_decode_gqa: q rows must start on 16-byte boundaries')
+        lse = torch.empty(B, H, device=q.device, dtype=torch.float32)
+        sp = _lib.load().mlc_attn_decode_splits(B, Hkv, max_len, int(splits))
+        part = decode_partials(q.device, B * H * sp * (D + 2)) if sp > 1 else None
+        _lib.call('mlc_attn_decode', _lib.ptr(q), q.stride(0) if B > 1 else H * D, _lib.ptr(kv_cache),
+                  _lib.ptr(seq_lens), _lib.ptr(part), _lib.ptr(ctx), _lib.ptr(lse), B, Smax, H, Hkv, D, max_len, sp,
+                  float(scale), _lib.stream())
+        return ctx, lse
+    G = H // Hkv
+    lse = torch.full((B, H), -math.inf)
+    ctx.zero_()
+    for b in range(B):
+        n = min(max(int(seq_lens[b]), 0), Smax)
+        if n == 0:
+            continue
+        k, v = kv_cache[b, :n].float().view(n, 2, Hkv, D).unbind(1)               # [n, Hkv, D] each
+        s = torch.einsum('jgd,njd->jgn', q[b].float().view(Hkv, G, D), k) * scale   # [Hkv, G, n]
+        lse[b] = torch.logsumexp(s, -1).reshape(H)
+        ctx[b] = torch.einsum('jgn,njd->jgd', torch.softmax(s, -1), v).reshape(H * D).to(torch.bfloat16)
+    return ctx, lse
+
+
+def kv_append_(kv_cache, qkv_rows, seq_lens, H, Hkv, head_dim: int = 64):
+    """Write the K/V columns [H*D, (H + 2*Hkv)*D) of packed row b of ``qkv_rows`` [B, (H + 2*Hkv)*D]
+    bf16 to ``kv_cache[b, seq_lens[b]]`` IN PLACE (``mlc_kv_append``) and return the cache; a position
+    outside [0, Smax) drops its row.  ``seq_lens`` is not advanced: the caller adds 1 with a torch
+    op, which a graph captures."""
+    D = head_dim
+    B, Smax = _decode_shapes(kv_cache, seq_lens, H, Hkv, D, 'kv_append_')
+    if (qkv_rows.dim() != 2 or tuple(qkv_rows.shape) != (B, (H + 2 * Hkv) * D) or qkv_rows.dtype != torch.bfloat16
+            or qkv_rows.stride(1) != 1):
+        raise ValueError(f'kv_append_: qkv_rows {tuple(qkv_rows.shape)} {qkv_rows.dtype} '
+                         f'(expected [{B}, {(H + 2 * Hkv) * D}] bfloat16 with unit inner stride)')
+    if _cuda(kv_cache):
+        if B > 1 and qkv_rows.stride(0) % 8 or qkv_rows.data_ptr() % 16:
+            raise ValueError('kv_append_: qkv_rows rows must start on 16-byte boundaries')
+        _lib.call('mlc_kv_append', _lib.ptr(qkv_rows), qkv_rows.stride(0) if B > 1 else (H + 2 * Hkv) * D,
+                  _lib.ptr(kv_cache), _lib.ptr(seq_lens), B, Smax, H, Hkv, D, _lib.stream())
+        return kv_cache
+    for b in range(B):
+        pos = int(seq_lens[b])
+        if 0 <= pos < Smax:
+            kv_cache[b, pos] = qkv_rows[b, H * D:]
+    return kv_cache
+
+
+__all__ = ['attn_decode_gqa', 'kv_append_', 'lm_loss_fwd', 'lm_loss_bwd', 'lm_head_loss', 'ln_fwd', 'ln_bwd', 'LnFinalizer', 'embed_bwd', 'embed_ln_fwd', 'embed_bwd_packed', 'cls_scatter', 'softmax_fwd', 'softmax_bwd', 'dense_fwd', 'dense_dgrad', 'dact_gelu', 'colsum_acc',
            'dropout', 'keep_mask', 'attn_fwd_varlen', 'attn_bwd_varlen', 'check_cu_seqlens',
            'attn_fwd_gqa', 'attn_bwd_gqa', 'attn_fwd_gqa_varlen', 'attn_bwd_gqa_varlen', 'rope_table', 'rope_qkv_', 'rms_fwd', 'rms_bwd', 'swiglu_fwd', 'swiglu_bwd',
            'decoder_native', 'set_decoder_native']
