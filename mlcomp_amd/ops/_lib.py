@@ -77,6 +77,8 @@ _SIGS = {
     'mlc_attn_decode_splits': [i32, i32, i32, i32],
     'mlc_attn_decode': [vp, i64] + [vp] * 5 + [i32] * 7 + [f32, vp],
     'mlc_kv_append': [vp, i64, vp, vp] + [i32] * 5 + [vp],
+    'mlc_attn_decode_paged': [vp, i64, vp, vp, i64] + [vp] * 4 + [i32] * 9 + [f32, vp],
+    'mlc_kv_append_paged': [vp, i64, vp, vp, i64, vp] + [i32] * 7 + [vp],
     'mlc_softmax_fwd': [vp] * 4 + [i64, i32, i32, f32, f32, vp, u32, vp],
     'mlc_softmax_bwd': [vp] * 3 + [i64, i32, f32, f32, vp, u32, vp],
     'mlc_linear_wgrad_bias': [vp] * 4 + [i32] * 7 + [vp, i64, vp],

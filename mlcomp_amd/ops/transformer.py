@@ -1204,15 +1204,21 @@ def lm_head_loss(hidden, weight, labels, ignore_index=-100, reduction='mean'):
 # csrc/kernels/attn_decode.hip: one new query row per sequence against kv_cache [B, Smax, 2*Hkv*D]
 # (K head j of a position at column j*D, V head j at (Hkv + j)*D: the tail of a packed qkv row).
 # The lengths are device data, so one captured graph serves every step of a generation.
+# With ``block_table`` (int32 [B, max_blocks]) the cache is a paged pool [num_blocks, page, 2*Hkv*D]:
+# entry [b, p] names the pool block that holds positions [p*page, (p + 1)*page) of sequence b.
 _DEC_PART = {}
 
 
-def _decode_shapes(kv_cache, seq_lens, H, Hkv, D, what):
+def _decode_heads(H, Hkv, D, what):
     G = _gqa_group(H, Hkv)
     if G > 16:
         raise ValueError(f'{what}: {G} query heads per key/value head (the kernel serves at most 16)')
     if D not in (64, 128):
         raise ValueError(f'{what}: head_dim {D} (expected 64 or 128)')
+
+
+def _decode_shapes(kv_cache, seq_lens, H, Hkv, D, what):
+    _decode_heads(H, Hkv, D, what)
     if kv_cache.dim() != 3 or kv_cache.shape[1] < 1 or kv_cache.shape[2] != 2 * Hkv * D:
         raise ValueError(f'{what}: kv_cache {tuple(kv_cache.shape)} (expected [B, Smax >= 1, 2*Hkv*D = {2 * Hkv * D}])')
     if kv_cache.dtype != torch.bfloat16 or seq_lens.dtype != torch.int32:
@@ -1221,6 +1227,40 @@ def _decode_shapes(kv_cache, seq_lens, H, Hkv, D, what):
         raise ValueError(f'{what}: seq_lens {tuple(seq_lens.shape)} for kv_cache {tuple(kv_cache.shape)} '
                          '(expected [B], both contiguous)')
     return kv_cache.shape[0], kv_cache.shape[1]
+
+
+def _paged_shapes(kv_pool, block_table, seq_lens, H, Hkv, D, what):
+    """(B, num_blocks, page, max_blocks) of a paged pool [num_blocks, page, 2*Hkv*D] and its block table"""
+    _decode_heads(H, Hkv, D, what)
+    if kv_pool.dim() != 3 or kv_pool.shape[0] < 1 or kv_pool.shape[2] != 2 * Hkv * D:
+        raise ValueError(f'{what}: kv_cache {tuple(kv_pool.shape)} with a block table '
+                         f'(expected [num_blocks >= 1, page, 2*Hkv*D = {2 * Hkv * D}])')
+    if kv_pool.shape[1] not in (16, 32, 64, 128):
+        raise ValueError(f'{what}: page size {kv_pool.shape[1]} (expected 16, 32, 64 or 128)')
+    if kv_pool.dtype != torch.bfloat16 or seq_lens.dtype != torch.int32 or block_table.dtype != torch.int32:
+        raise ValueError(f'{what}: kv_cache {kv_pool.dtype}, seq_lens {seq_lens.dtype}, block_table {block_table.dtype} '
+                         '(expected bfloat16, int32, int32)')
+    if (block_table.dim() != 2 or block_table.shape[1] < 1 or block_table.stride(1) != 1
+            or block_table.shape[0] > 1 and block_table.stride(0) < block_table.shape[1]):
+        raise ValueError(f'{what}: block_table {tuple(block_table.shape)} strides {tuple(block_table.stride())} '
+                         '(expected [B, max_blocks >= 1] with unit inner stride, rows not overlapping)')
+    if (tuple(seq_lens.shape) != (block_table.shape[0],) or not kv_pool.is_contiguous() or not seq_lens.is_contiguous()
+            or block_table.device != kv_pool.device):
+        raise ValueError(f'{what}: seq_lens {tuple(seq_lens.shape)} for block_table {tuple(block_table.shape)} '
+                         '(expected [B]; kv_cache and seq_lens contiguous, the table on the cache\'s device)')
+    if block_table.shape[1] * kv_pool.shape[1] >= 2 ** 31 - 512:
+        raise ValueError(f'{what}: {block_table.shape[1]} blocks of {kv_pool.shape[1]} positions per sequence '
+                         '(at most 2^31 - 512 positions)')
+    return block_table.shape[0], kv_pool.shape[0], kv_pool.shape[1], block_table.shape[1]
+
+
+def _gather_pages(kv_pool, block_table):
+    """The logical contiguous cache [B, max_blocks*page, W] of a paged pool (CPU twin); blocks that the
+    table does not name (ids outside the pool) read as zeros."""
+    nblk, page, W = kv_pool.shape
+    ok = (block_table >= 0) & (block_table < nblk)
+    pages = kv_pool[block_table.long().clamp(0, nblk - 1)]
+    return torch.where(ok[:, :, None, None], pages, torch.zeros_like(pages)).reshape(block_table.shape[0], -1, W)
 
 
 def decode_partials(device, n: int) -> torch.Tensor:
@@ -1238,7 +1278,7 @@ def decode_partials(device, n: int) -> torch.Tensor:
 
 
 def attn_decode_gqa(q, kv_cache, seq_lens, H, Hkv, scale, head_dim: int = 64, *, max_len=None, splits: int = 0,
-                    out=None):
+                    out=None, block_table=None):
     """One decode step of grouped-query attention: query row b (``q`` [B, H*D] bf16, unit inner
     stride, any row stride: the Q columns of the step's packed projection output pass as a view)
     against the first ``seq_lens[b]`` positions of ``kv_cache`` [B, Smax, 2*Hkv*D] bf16, query head h
@@ -1246,9 +1286,19 @@ def attn_decode_gqa(q, kv_cache, seq_lens, H, Hkv, scale, head_dim: int = 64, *,
     (ctx [B, H*D] bf16, lse [B, H] fp32 = log sum exp(scale * q.k)); a length of 0 gives ctx = 0 and
     lse = -inf; cache rows at or past the length are never used (they may hold NaN).  ``max_len``: a
     host-side upper bound of the lengths (default Smax) that sizes the key splits; ``splits``: 0 =
-    chosen to fill the chip (``mlc_attn_decode_splits``).  ``out``: a contiguous [B, H*D] bf16 ctx."""
+    chosen to fill the chip (``mlc_attn_decode_splits``).  ``out``: a contiguous [B, H*D] bf16 ctx.
+    ``block_table`` (int32 [B, max_blocks], unit inner stride, any row stride, on the device): ``kv_cache``
+    is a paged pool [num_blocks, page, 2*Hkv*D] with page 16 / 32 / 64 / 128, position n of sequence b is row
+    ``n % page`` of block ``block_table[b, n // page]``, and Smax is ``max_blocks * page``
+    (``mlc_attn_decode_paged``).  Table entries at or past ``ceil(seq_lens[b] / page)`` are not read; a
+    block id outside the pool reads as zeros.  With the same split count the result is bit-equal to the
+    contiguous call on the same logical data."""
     D = head_dim
-    B, Smax = _decode_shapes(kv_cache, seq_lens, H, Hkv, D, 'attn_decode_gqa')
+    if block_table is not None:
+        B, nblk, page, maxb = _paged_shapes(kv_cache, block_table, seq_lens, H, Hkv, D, 'attn_decode_gqa')
+        Smax = maxb * page
+    else:
+        B, Smax = _decode_shapes(kv_cache, seq_lens, H, Hkv, D, 'attn_decode_gqa')
     if q.dim() != 2 or tuple(q.shape) != (B, H * D) or q.dtype != torch.bfloat16 or q.stride(1) != 1:
         raise ValueError(f'attn_decode_gqa: q {tuple(q.shape)} {q.dtype} strides {tuple(q.stride())} '
                          f'(expected [{B}, {H * D}] bfloat16 with unit inner stride)')
@@ -1262,10 +1312,18 @@ def attn_decode_gqa(q, kv_cache, seq_lens, H, Hkv, scale, head_dim: int = 64, *,
         lse = torch.empty(B, H, device=q.device, dtype=torch.float32)
         sp = _lib.load().mlc_attn_decode_splits(B, Hkv, max_len, int(splits))
         part = decode_partials(q.device, B * H * sp * (D + 2)) if sp > 1 else None
+        if block_table is not None:
+            _lib.call('mlc_attn_decode_paged', _lib.ptr(q), q.stride(0) if B > 1 else H * D, _lib.ptr(kv_cache),
+                      _lib.ptr(block_table), block_table.stride(0) if B > 1 else maxb, _lib.ptr(seq_lens), _lib.ptr(part),
+                      _lib.ptr(ctx),
+                      _lib.ptr(lse), B, nblk, page, maxb, H, Hkv, D, max_len, sp, float(scale), _lib.stream())
+            return ctx, lse
         _lib.call('mlc_attn_decode', _lib.ptr(q), q.stride(0) if B > 1 else H * D, _lib.ptr(kv_cache),
                   _lib.ptr(seq_lens), _lib.ptr(part), _lib.ptr(ctx), _lib.ptr(lse), B, Smax, H, Hkv, D, max_len, sp,
                   float(scale), _lib.stream())
         return ctx, lse
+    if block_table is not None:
+        kv_cache = _gather_pages(kv_cache, block_table)
     G = H // Hkv
     lse = torch.full((B, H), -math.inf)
     ctx.zero_()
@@ -1280,13 +1338,19 @@ def attn_decode_gqa(q, kv_cache, seq_lens, H, Hkv, scale, head_dim: int = 64, *,
     return ctx, lse
 
 
-def kv_append_(kv_cache, qkv_rows, seq_lens, H, Hkv, head_dim: int = 64):
+def kv_append_(kv_cache, qkv_rows, seq_lens, H, Hkv, head_dim: int = 64, *, block_table=None):
     """Write the K/V columns [H*D, (H + 2*Hkv)*D) of packed row b of ``qkv_rows`` [B, (H + 2*Hkv)*D]
     bf16 to ``kv_cache[b, seq_lens[b]]`` IN PLACE (``mlc_kv_append``) and return the cache; a position
     outside [0, Smax) drops its row.  ``seq_lens`` is not advanced: the caller adds 1 with a torch
-    op, which a graph captures."""
+    op, which a graph captures.  With ``block_table`` (see :func:`attn_decode_gqa`) the row goes to
+    ``kv_cache[block_table[b, pos // page], pos % page]`` of the paged pool (``mlc_kv_append_paged``); a
+    position outside [0, max_blocks * page) or a block id outside the pool drops its row."""
     D = head_dim
-    B, Smax = _decode_shapes(kv_cache, seq_lens, H, Hkv, D, 'kv_append_')
+    if block_table is not None:
+        B, nblk, page, maxb = _paged_shapes(kv_cache, block_table, seq_lens, H, Hkv, D, 'kv_append_')
+        Smax = maxb * page
+    else:
+        B, Smax = _decode_shapes(kv_cache, seq_lens, H, Hkv, D, 'kv_append_')
     if (qkv_rows.dim() != 2 or tuple(qkv_rows.shape) != (B, (H + 2 * Hkv) * D) or qkv_rows.dtype != torch.bfloat16
             or qkv_rows.stride(1) != 1):
         raise ValueError(f'kv_append_: qkv_rows {tuple(qkv_rows.shape)} {qkv_rows.dtype} '
@@ -1294,13 +1358,22 @@ def kv_append_(kv_cache, qkv_rows, seq_lens, H, Hkv, head_dim: int = 64):
     if _cuda(kv_cache):
         if B > 1 and qkv_rows.stride(0) % 8 or qkv_rows.data_ptr() % 16:
             raise ValueError('kv_append_: qkv_rows rows must start on 16-byte boundaries')
+        if block_table is not None:
+            _lib.call('mlc_kv_append_paged', _lib.ptr(qkv_rows), qkv_rows.stride(0) if B > 1 else (H + 2 * Hkv) * D,
+                      _lib.ptr(kv_cache), _lib.ptr(block_table), block_table.stride(0) if B > 1 else maxb,
+                      _lib.ptr(seq_lens), B, nblk, page, maxb, H, Hkv, D, _lib.stream())
+            return kv_cache
         _lib.call('mlc_kv_append', _lib.ptr(qkv_rows), qkv_rows.stride(0) if B > 1 else (H + 2 * Hkv) * D,
                   _lib.ptr(kv_cache), _lib.ptr(seq_lens), B, Smax, H, Hkv, D, _lib.stream())
         return kv_cache
     for b in range(B):
         pos = int(seq_lens[b])
-        if 0 <= pos < Smax:
+        if not 0 <= pos < Smax:
+            continue
+        if block_table is None:
             kv_cache[b, pos] = qkv_rows[b, H * D:]
+        elif 0 <= int(block_table[b, pos // page]) < nblk:
+            kv_cache[int(block_table[b, pos // page]), pos % page] = qkv_rows[b, H * D:]
     return kv_cache
 
 
